@@ -7,6 +7,13 @@ ring all-reduce runs every H=100 inner steps (and once during warmup so the
 path is exercised even when K < H). Rank 0 prints ONE JSON line with the
 whole-job tokens/sec.
 
+A plain run does only what the headline needs: set up, warm up (including
+the one timed outer sync the headline amortizes), time K steps, print the
+line. `--dump-outputs DIR` additionally writes what the last timed step
+produced as DIR/<name>.npy (same arguments -> same seeds and inputs, so
+two builds can be compared output for output). Secondary measurements
+belong behind `--full`.
+
 Host-memory sizing at N=8 x 10B: each rank keeps fp32 theta_outer +
 momentum on the host (2 x 42 GB), i.e. ~672 GB across the node; the
 allocation is pinned only when MemAvailable comfortably covers it
@@ -17,9 +24,42 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import tempfile
 import time
 
 import torch
+
+
+# --dump-outputs: elements sampled from each flat tensor (3 x 16 MiB as fp32)
+_DUMP_SAMPLE = 1 << 22
+
+
+def dump_outputs(trainer, loss, out_dir: str) -> None:
+    """Write what the last timed train_step() left its caller: the returned
+    loss and the state it updated in place (bf16 weights, fp32 master
+    weights, gradients). The flat tensors are too large to store whole, so
+    a fixed seeded index sample of each is written, as float32 .npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = trainer.flat
+    n = flat.flat_w.numel()
+    if n > _DUMP_SAMPLE:
+        g = torch.Generator()
+        g.manual_seed(0)
+        idx = torch.randint(0, n, (_DUMP_SAMPLE,), generator=g).sort().values
+    else:
+        idx = torch.arange(n)
+    idx = idx.to(flat.flat_w.device)
+    arrays = {
+        "loss": torch.zeros(1) if loss is None else loss.reshape(1),
+        "weights_sample": flat.flat_w.index_select(0, idx),
+        "master_weights_sample": flat.master32.index_select(0, idx),
+        "grads_sample": flat.flat_grad.index_select(0, idx),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                t.detach().float().cpu().numpy())
 
 
 def main() -> None:
@@ -42,6 +82,12 @@ def main() -> None:
     ap.add_argument("--ckpt", choices=["on", "off"], default="off",
                     help="activation checkpointing (off: 288 GB HBM fits the "
                          "10B config's activations; recompute costs ~25%%)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step produced (loss, seeded samples of the weights, "
+                         "fp32 master weights and gradients) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (none yet)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -69,7 +115,11 @@ def main() -> None:
         diloco=DilocoConfig(H=args.h, quant_int8=True, outer_device="auto"),
         metrics=MetricsConfig(log_interval=10**9),
     )
-    trainer = Trainer(cfg, run_dir=os.environ.get("BENCH_RUN_DIR", "/tmp/prime_amd_bench"))
+    # per-user default: a fixed name in a shared temp dir left behind by
+    # another account is not writable
+    run_dir = os.environ.get("BENCH_RUN_DIR") or os.path.join(
+        tempfile.gettempdir(), f"prime_amd_bench_{os.getuid()}")
+    trainer = Trainer(cfg, run_dir=run_dir)
     dev = trainer.device
 
     # ---- warmup (incl. one outer sync so ring/host-offload path is hot).
@@ -95,9 +145,10 @@ def main() -> None:
 
     # ---- timed region
     outer_before = trainer.diloco.outer_step_count
+    loss = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        trainer.train_step()
+        loss = trainer.train_step()
     if dev.type == "cuda":
         torch.cuda.synchronize()
     trainer.mesh.barrier()
@@ -132,6 +183,9 @@ def main() -> None:
     tps = total_tokens / elapsed_incl
     tps_gpu = tps / n_gpus
     mfu = mfu_of(tps_gpu, trainer.flops_per_token)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(trainer, loss, args.dump_outputs)
 
     if rank == 0:
         print(json.dumps({

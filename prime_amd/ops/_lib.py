@@ -20,14 +20,15 @@ _TRIED = False
 _SIGS = {
     # name -> argtypes (all return c_int hipError_t)
     "prime_rmsnorm_fwd": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 2 + [ctypes.c_double],
-    "prime_rmsnorm_bwd": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 2 + [ctypes.c_double],
+    "prime_rmsnorm_bwd": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 3 + [ctypes.c_double],
     "prime_add_rmsnorm_fwd": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 2 + [ctypes.c_double],
-    "prime_add_rmsnorm_bwd": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 2 + [ctypes.c_double],
+    "prime_add_rmsnorm_bwd": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 3 + [ctypes.c_double],
     "prime_rope": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 4 + [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p],
     "prime_swiglu_fwd": [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 2,
     "prime_swiglu_bwd": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 2,
     "prime_adamw": [ctypes.c_void_p] * 7 + [ctypes.c_int64] + [ctypes.c_double] * 5 + [ctypes.c_int64],
-    "prime_grad_sqnorm": [ctypes.c_void_p] * 3 + [ctypes.c_int64],
+    "prime_grad_sqnorm": [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 2,
+    "prime_grad_sqnorm_partials": [],
     "prime_pseudograd": [ctypes.c_void_p] * 4 + [ctypes.c_int64],
     "prime_quant_int8": [ctypes.c_void_p] * 4 + [ctypes.c_int64],
     "prime_dequant_int8": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 2,

@@ -67,9 +67,12 @@ PRIME_API int prime_adamw(hipStream_t stream, void* p32, void* p16,
   return (int)hipGetLastError();
 }
 
-// single-pass squared L2 norm of a bf16 buffer (fp32 accumulation)
-__global__ void sqnorm_kernel(const bf16* __restrict__ g, float* __restrict__ out,
-                              int64_t N) {
+// single-pass squared L2 norm of a bf16 buffer (fp32 accumulation). Each
+// block stores its partial sum; the caller adds the partials up in a fixed
+// order, so the result is the same bits every run (float atomics onto one
+// word are not: their order varies)
+__global__ void sqnorm_kernel(const bf16* __restrict__ g,
+                              float* __restrict__ partials, int64_t N) {
   __shared__ float scratch[16];
   float acc = 0.f;
   const int64_t nv = N / 8;
@@ -88,13 +91,18 @@ __global__ void sqnorm_kernel(const bf16* __restrict__ g, float* __restrict__ ou
     acc += f * f;
   }
   acc = block_reduce_sum(acc, scratch);
-  if (threadIdx.x == 0) atomicAdd(out, acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
-PRIME_API int prime_grad_sqnorm(hipStream_t stream, const void* g, void* out,
-                                int64_t N) {
+// how many partials prime_grad_sqnorm may write (its grid cap)
+PRIME_API int prime_grad_sqnorm_partials(void) { return PRIME_MAX_GRID; }
+
+// partials: n_partials pre-zeroed floats, n_partials >= the count above
+PRIME_API int prime_grad_sqnorm(hipStream_t stream, const void* g,
+                                void* partials, int64_t N, int64_t n_partials) {
   int grid = prime_grid(N / 8 + 1, 256);
+  if (n_partials < grid) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sqnorm_kernel, dim3(grid), dim3(256), 0, stream,
-                     (const bf16*)g, (float*)out, N);
+                     (const bf16*)g, (float*)partials, N);
   return (int)hipGetLastError();
 }

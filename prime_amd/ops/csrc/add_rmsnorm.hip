@@ -50,14 +50,16 @@ __global__ void add_rmsnorm_fwd_kernel(const bf16* __restrict__ x,
   }
 }
 
-// ds = ds_res + rstd*(dy*w - shat*mean(dy*w*shat)) ; dw += sum dy*shat
+// ds = ds_res + rstd*(dy*w - shat*mean(dy*w*shat)) ;
+// dw_part[block, :] = sum over the block's rows of dy*shat (summed by the
+// caller in a fixed order, see rmsnorm.hip)
 __global__ void add_rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
                                        const bf16* __restrict__ ds_res,
                                        const bf16* __restrict__ s,
                                        const bf16* __restrict__ w,
                                        const float* __restrict__ rstd,
                                        bf16* __restrict__ ds_out,
-                                       float* __restrict__ dw, int64_t R,
+                                       float* __restrict__ dw_part, int64_t R,
                                        int D, float eps) {
   extern __shared__ float lds[];
   float* dw_loc = lds;
@@ -100,7 +102,7 @@ __global__ void add_rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
     __syncthreads();
   }
   for (int i = tid; i < D; i += nthr)
-    if (dw_loc[i] != 0.f) atomicAdd(&dw[i], dw_loc[i]);
+    dw_part[(int64_t)blockIdx.x * D + i] = dw_loc[i];
 }
 
 PRIME_API int prime_add_rmsnorm_fwd(hipStream_t stream, const void* x,
@@ -119,16 +121,16 @@ PRIME_API int prime_add_rmsnorm_fwd(hipStream_t stream, const void* x,
 PRIME_API int prime_add_rmsnorm_bwd(hipStream_t stream, const void* dy,
                                     const void* ds_res, const void* s,
                                     const void* w, const void* rstd,
-                                    void* ds_out, void* dw, int64_t R,
-                                    int64_t D, double eps) {
+                                    void* ds_out, void* dw_part, int64_t R,
+                                    int64_t D, int64_t dw_rows, double eps) {
   if (D % 8 != 0) return hipErrorInvalidValue;
-  int grid = prime_grid(R, 1);
-  if (grid > 1024) grid = 1024;
+  if (dw_rows < 1 || dw_rows > 1024) return hipErrorInvalidValue;
+  int grid = (int)dw_rows;
   size_t lds = (size_t)(D + 16) * sizeof(float);
   if (lds > 160 * 1024 - 1024) return hipErrorInvalidValue;
   hipLaunchKernelGGL(add_rmsnorm_bwd_kernel, dim3(grid), dim3(256), lds,
                      stream, (const bf16*)dy, (const bf16*)ds_res,
                      (const bf16*)s, (const bf16*)w, (const float*)rstd,
-                     (bf16*)ds_out, (float*)dw, R, (int)D, (float)eps);
+                     (bf16*)ds_out, (float*)dw_part, R, (int)D, (float)eps);
   return (int)hipGetLastError();
 }

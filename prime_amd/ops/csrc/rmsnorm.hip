@@ -2,8 +2,10 @@
 //
 // Memory-bound: vectorized bf16x8 loads (16 B/lane), fp32 accumulation,
 // one 256-thread block per row (grid-stride over rows). Backward
-// accumulates dw into an LDS fp32 buffer per block, then one atomicAdd
-// pass per block (device-scope atomics are XCD-safe, guide §6 G12).
+// accumulates dw into an LDS fp32 buffer per block and stores it as that
+// block's row of a [grid, D] partial buffer; the caller sums the rows in a
+// fixed order (float atomics onto dw would make the sum order, and so the
+// last bits of dw, vary from run to run).
 //
 // Mirrors the capability of the reference framework's fused norm path
 // (SURVEY.md §B3); numerics checked against PyTorch fp32 reference in
@@ -46,13 +48,13 @@ __global__ void rmsnorm_fwd_kernel(const bf16* __restrict__ x,
 }
 
 // dx = rstd * (dy*w - xhat * mean(dy*w*xhat)), xhat = x*rstd
-// dw += sum_r dy * xhat   (fp32 accumulation in LDS, then global atomics)
+// dw_part[block, :] = sum over the block's rows of dy * xhat   (fp32, LDS)
 __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
                                    const bf16* __restrict__ x,
                                    const bf16* __restrict__ w,
                                    const float* __restrict__ rstd,
                                    bf16* __restrict__ dx,
-                                   float* __restrict__ dw,
+                                   float* __restrict__ dw_part,
                                    int64_t R, int D, float eps) {
   extern __shared__ float lds[];        // [D] dw accumulator + 16 scratch
   float* dw_loc = lds;
@@ -94,7 +96,7 @@ __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
                       // keep row boundary ordered with the reduction scratch
   }
   for (int i = tid; i < D; i += nthr)
-    if (dw_loc[i] != 0.f) atomicAdd(&dw[i], dw_loc[i]);
+    dw_part[(int64_t)blockIdx.x * D + i] = dw_loc[i];
 }
 
 PRIME_API int prime_rmsnorm_fwd(hipStream_t stream, const void* x, const void* w,
@@ -110,15 +112,18 @@ PRIME_API int prime_rmsnorm_fwd(hipStream_t stream, const void* x, const void* w
 
 PRIME_API int prime_rmsnorm_bwd(hipStream_t stream, const void* dy, const void* x,
                                 const void* w, const void* rstd, void* dx,
-                                void* dw, int64_t R, int64_t D, double eps) {
+                                void* dw_part, int64_t R, int64_t D,
+                                int64_t dw_rows, double eps) {
   if (D % 8 != 0) return hipErrorInvalidValue;
-  int grid = prime_grid(R, 1);
-  if (grid > 1024) grid = 1024;  // bound atomic traffic on dw
+  // one block per row of dw_part [dw_rows, D]; every block writes its row
+  // (zeros if it has no input row, so R == 0 gives dw = 0)
+  if (dw_rows < 1 || dw_rows > 1024) return hipErrorInvalidValue;
+  int grid = (int)dw_rows;
   size_t lds = (size_t)(D + 16) * sizeof(float);
   if (lds > 160 * 1024 - 1024) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rmsnorm_bwd_kernel, dim3(grid), dim3(256), lds, stream,
                      (const bf16*)dy, (const bf16*)x, (const bf16*)w,
-                     (const float*)rstd, (bf16*)dx, (float*)dw, R, (int)D,
+                     (const float*)rstd, (bf16*)dx, (float*)dw_part, R, (int)D,
                      (float)eps);
   return (int)hipGetLastError();
 }

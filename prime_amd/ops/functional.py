@@ -12,6 +12,11 @@ import torch
 from . import reference as ref
 from ._lib import check, lib, ptr, stream_of
 
+# reductions that cross thread blocks store one partial per block and are
+# summed here in a fixed order, never with float atomics, so a step's
+# results are bit-identical from run to run
+_DW_ROWS = 1024  # max blocks (= partial dw rows) of the norm backwards
+
 
 def _is_hip(t: torch.Tensor) -> bool:
     return t.is_cuda
@@ -60,14 +65,16 @@ class _RMSNorm(torch.autograd.Function):
         D = x.shape[-1]
         R = x.numel() // D
         dx = torch.empty_like(x)
-        dw = torch.zeros(D, device=x.device, dtype=torch.float32)
+        # per-block partial dw rows, summed in a fixed order (deterministic)
+        G = max(1, min(R, _DW_ROWS))
+        dw = torch.empty(G, D, device=x.device, dtype=torch.float32)
         check(
             lib().prime_rmsnorm_bwd(
-                stream_of(x), ptr(dy), ptr(x), ptr(w), ptr(rstd), ptr(dx), ptr(dw), R, D, ctx.eps
+                stream_of(x), ptr(dy), ptr(x), ptr(w), ptr(rstd), ptr(dx), ptr(dw), R, D, G, ctx.eps
             ),
             "rmsnorm_bwd",
         )
-        return dx, dw.to(w.dtype), None
+        return dx, dw.sum(0).to(w.dtype), None
 
 
 def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
@@ -656,8 +663,14 @@ def fused_adamw(p32, p16, grad, m, v, *, lr, beta1, beta2, eps, wd, step,
 
 def grad_sqnorm(grad: torch.Tensor, out: torch.Tensor) -> None:
     """out (1-elem fp32, pre-zeroed) += sum(grad^2), single bf16 pass."""
-    check(lib().prime_grad_sqnorm(stream_of(grad), ptr(grad), ptr(out), grad.numel()),
+    # per-block partials added up in a fixed order: the clip scale, and so
+    # every weight update, is bit-identical from run to run
+    part = torch.zeros(lib().prime_grad_sqnorm_partials(), device=grad.device,
+                       dtype=torch.float32)
+    check(lib().prime_grad_sqnorm(stream_of(grad), ptr(grad), ptr(part),
+                                  grad.numel(), part.numel()),
           "grad_sqnorm")
+    out.add_(part.sum())
 
 
 def pseudograd(outer32, master32, out_delta):
@@ -762,16 +775,17 @@ class _AddRMSNorm(torch.autograd.Function):
         D = s.shape[-1]
         R = s.numel() // D
         ds = torch.empty_like(s)
-        dw = torch.zeros(D, device=s.device, dtype=torch.float32)
+        G = max(1, min(R, _DW_ROWS))
+        dw = torch.empty(G, D, device=s.device, dtype=torch.float32)
         dres_in = ds_res.contiguous() if ds_res is not None else None
         check(
             lib().prime_add_rmsnorm_bwd(
                 stream_of(s), ptr(dy), ptr(dres_in), ptr(s), ptr(w), ptr(rstd),
-                ptr(ds), ptr(dw), R, D, ctx.eps,
+                ptr(ds), ptr(dw), R, D, G, ctx.eps,
             ),
             "add_rmsnorm_bwd",
         )
-        return ds, (ds if ctx.needs_input_grad[1] else None), dw.to(w.dtype), None
+        return ds, (ds if ctx.needs_input_grad[1] else None), dw.sum(0).to(w.dtype), None
 
 
 def fused_add_rmsnorm(x, res, w, eps: float = 1e-5):

@@ -1,6 +1,7 @@
 import os
 import socket
 import sys
+import tempfile
 from pathlib import Path
 
 import pytest
@@ -8,6 +9,10 @@ import pytest
 REPO = Path(__file__).resolve().parent.parent
 if str(REPO) not in sys.path:
     sys.path.insert(0, str(REPO))
+
+# run directories of the tests: per user, because a fixed name in a shared
+# temp dir that another account created first is not writable
+SCRATCH = Path(tempfile.gettempdir()) / f"prime_amd_test_{os.getuid()}"
 
 
 def pytest_configure(config):

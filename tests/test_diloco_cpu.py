@@ -1,7 +1,7 @@
 """DiLoCo plumbing on CPU/gloo (BASELINE.json config 1: runs without GPUs)."""
 import torch
 
-from tests.conftest import run_distributed
+from tests.conftest import SCRATCH, run_distributed
 
 
 def _diloco_worker(rank, world, steps, H, quant):
@@ -18,7 +18,7 @@ def _diloco_worker(rank, world, steps, H, quant):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/diloco_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/diloco_r{rank}")
     res = tr.run()
     # after a final outer step, params equal across workers
     flat_after = tr.flat.flat_w.clone()
@@ -71,7 +71,7 @@ def _mixed_worker(rank, world):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/mixed_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/mixed_r{rank}")
     res = tr.run()
     out = {
         "outer": res["outer_steps"],
@@ -106,7 +106,7 @@ def _soak_worker(rank, world, steps, h):
         metrics=MetricsConfig(log_interval=1000),
     )
     cfg.data.micro_batch_size = 1
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/soak8_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/soak8_r{rank}")
     for _ in range(steps):
         tr.train_step()
     head = tr.diloco.theta_outer[:16].tolist()

@@ -8,7 +8,7 @@ import time
 import pytest
 import torch
 
-from tests.conftest import free_port
+from tests.conftest import SCRATCH, free_port
 
 
 def _spawn(fns_envs, timeout=180):
@@ -190,7 +190,7 @@ def _elastic_trainer(port, host, steps):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/elastic_{host}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/elastic_{host}")
     # both workers must be registered before the first boundary so the
     # first view has world=2 (otherwise the test's equality check is moot)
     while len(tr.elastic.members()) < 2:
@@ -349,7 +349,7 @@ def _departing_trainer(port, host, steps):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/depart_{host}_{steps}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/depart_{host}_{steps}")
     while len(tr.elastic.members()) < 2:
         time.sleep(0.05)
     res = tr.run()

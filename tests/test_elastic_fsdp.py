@@ -9,7 +9,7 @@ import time
 import pytest
 import torch
 
-from tests.conftest import free_port
+from tests.conftest import SCRATCH, free_port
 from tests.test_elastic import _entry
 
 
@@ -56,7 +56,7 @@ def _fsdp_trainer(gport, host, steps, run_tag):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/elfsdp_{run_tag}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/elfsdp_{run_tag}")
     import torch.distributed as dist
 
     # both workers registered before the first boundary
@@ -265,7 +265,7 @@ def _failover_worker(gport, idx):
     # coordinate the store restart through files (the store dies)
     import pathlib
 
-    flagdir = pathlib.Path("/tmp/prime_amd_test/failover")
+    flagdir = pathlib.Path(SCRATCH / "failover")
     flagdir.mkdir(parents=True, exist_ok=True)
     (flagdir / f"synced{idx}").write_text("1")
     while not (flagdir / "store_restarted").exists():
@@ -288,7 +288,7 @@ def test_store_host_failover():
     import pathlib
     import shutil
 
-    shutil.rmtree("/tmp/prime_amd_test/failover", ignore_errors=True)
+    shutil.rmtree(SCRATCH / "failover", ignore_errors=True)
     gport = free_port()
     ctx = mp.get_context("spawn")
     ready, stop = ctx.Event(), ctx.Event()
@@ -302,7 +302,7 @@ def test_store_host_failover():
         pr = ctx.Process(target=_entry, args=(_failover_worker, i, {}, (gport, i), q))
         pr.start()
         procs.append(pr)
-    flagdir = pathlib.Path("/tmp/prime_amd_test/failover")
+    flagdir = pathlib.Path(SCRATCH / "failover")
     t0 = time.monotonic()
     while not all((flagdir / f"synced{i}").exists() for i in range(2)):
         assert time.monotonic() - t0 < 60

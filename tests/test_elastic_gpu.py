@@ -7,7 +7,7 @@ import time
 import pytest
 import torch
 
-from tests.conftest import free_port
+from tests.conftest import SCRATCH, free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +33,7 @@ def _worker(idx, port, host, q):
             metrics=MetricsConfig(log_interval=100),
         )
         cfg.data.micro_batch_size = 1
-        tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/elgpu_{idx}")
+        tr = Trainer(cfg, run_dir=f"{SCRATCH}/elgpu_{idx}")
         assert tr.device.type == "cuda"
         while len(tr.elastic.members()) < 2:
             time.sleep(0.05)

@@ -2,7 +2,7 @@
 2-rank data-parallel training (same seed, same data shards)."""
 import torch
 
-from tests.conftest import run_distributed
+from tests.conftest import SCRATCH, run_distributed
 
 
 def _train_worker(rank, world, fsdp, steps):
@@ -21,7 +21,7 @@ def _train_worker(rank, world, fsdp, steps):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/fsdp{fsdp}_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/fsdp{fsdp}_r{rank}")
     losses = []
     for _ in range(steps):
         losses.append(float(tr.train_step()))
@@ -71,7 +71,7 @@ def _fsdp_diloco_worker(rank, world):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/fsdp_diloco_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/fsdp_diloco_r{rank}")
     res = tr.run()
     out = (res["outer_steps"], float(tr.flat.flat_w.float().sum()))
     tr.close()
@@ -245,7 +245,7 @@ def _consensus_stop_worker(rank, world):
         metrics=MetricsConfig(log_interval=1000),
     )
     cfg.data.micro_batch_size = 1
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/stopc_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/stopc_r{rank}")
     steps_done = 0
     orig = tr.train_step
 

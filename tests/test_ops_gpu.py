@@ -56,6 +56,66 @@ def test_rmsnorm_fwd_bwd():
     torch.testing.assert_close(w.grad.float().cpu(), wr.grad, atol=0.1, rtol=3e-2)
 
 
+def test_cross_block_reductions_are_repeatable():
+    """dw of both norm backwards and the gradient square norm are summed
+    across thread blocks in a fixed order: repeated calls on the same input
+    give the same bits (a float-atomic sum does not), and dw stays correct
+    when there are more rows than the 1024 partial rows (R = 2500, odd).
+
+    dw tolerance: the sum is kept in fp32 and rounded once to bf16, so
+    |err| <= 2^-8 |dw| (rtol 2^-7 leaves a factor 2) plus the fp32
+    accumulation error, at most R * 2^-24 * max|term| ~ 2500 * 6e-8 * 25
+    = 4e-3 (atol)."""
+    from prime_amd import ops
+
+    R, D = 2500, 512
+    x = _bf(torch.randn(R, D))
+    res = _bf(torch.randn(R, D))
+    w = _bf(torch.randn(D))
+    dy = _bf(torch.randn(R, D))
+
+    def norm_dw():
+        wl = w.clone().requires_grad_(True)
+        ops.rmsnorm(x, wl).backward(dy)
+        return wl.grad
+
+    def add_norm_dw():
+        wl = w.clone().requires_grad_(True)
+        xl = x.clone().requires_grad_(True)
+        y, s = ops.fused_add_rmsnorm(xl, res, wl)
+        torch.autograd.backward([y, s], [dy, dy])
+        return wl.grad
+
+    def sqnorm():
+        sq = torch.zeros(1, device=DEV)
+        ops.grad_sqnorm(g, sq)
+        return sq
+
+    g = _bf(torch.randn(2048 * 256 * 8 + 4099) * 3)  # grid at its cap + tail
+    for fn in (norm_dw, add_norm_dw, sqnorm):
+        first = fn()
+        for _ in range(4):
+            assert torch.equal(fn(), first), fn.__name__
+
+    for s_in, got in ((x, norm_dw()), (x.float() + res.float(), add_norm_dw())):
+        sf = s_in.float().cpu()
+        rstd = torch.rsqrt(sf.pow(2).mean(-1, keepdim=True) + 1e-5)
+        # as the kernel: rstd from the fp32 sum, xhat from the stored bf16 sum
+        xhat = sf.bfloat16().float() * rstd
+        want = (dy.double().cpu() * xhat.double()).sum(0).float()
+        torch.testing.assert_close(got.float().cpu(), want, rtol=2**-7, atol=4e-3)
+    # no rows at all: dw is zero, not an error
+    wl = w.clone().requires_grad_(True)
+    ops.rmsnorm(x[:0], wl).backward(dy[:0])
+    y, s = ops.fused_add_rmsnorm(x[:0].clone().requires_grad_(True), res[:0], wl)
+    torch.autograd.backward([y, s], [dy[:0], dy[:0]])
+    assert wl.grad.shape == w.shape and torch.count_nonzero(wl.grad) == 0
+    # positive terms, fp32: 64 serial adds per thread then trees, error well
+    # under 100 ulp = 6e-6 relative
+    want = g.double().pow(2).sum().float().cpu().reshape(1)
+    torch.testing.assert_close(sqnorm().cpu(), want, rtol=1e-5, atol=0)
+
+
 def test_rope_fwd_bwd():
     from prime_amd import ops
     from prime_amd.ops import reference as ref

@@ -3,7 +3,7 @@ round-trip, gradient flow, and a 2-rank SP Trainer matching a 1-rank
 full-context run exactly (same seed/data)."""
 import torch
 
-from tests.conftest import run_distributed
+from tests.conftest import SCRATCH, run_distributed
 
 
 def _a2a_worker(rank, world):
@@ -73,7 +73,7 @@ def _sp_trainer(rank, world, sp, steps):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/sp{sp}_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/sp{sp}_r{rank}")
     losses = []
     for _ in range(steps):
         loss = tr.train_step()
@@ -123,7 +123,7 @@ def _sp_diloco_trainer(rank, world, sp, steps):
         metrics=MetricsConfig(log_interval=100),
     )
     cfg.data.micro_batch_size = 2
-    tr = Trainer(cfg, run_dir=f"/tmp/prime_amd_test/spd{sp}_r{rank}")
+    tr = Trainer(cfg, run_dir=f"{SCRATCH}/spd{sp}_r{rank}")
     losses = []
     for _ in range(steps):
         loss = tr.train_step()

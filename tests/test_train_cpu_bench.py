@@ -1,6 +1,7 @@
 """Guards the driver contract: bench.py single- and multi-rank invocations
 must emit exactly one well-formed JSON line from rank 0."""
 import json
+import os
 import subprocess
 import sys
 from pathlib import Path
@@ -32,6 +33,34 @@ def test_bench_single_rank_cpu():
     )
     assert out.returncode == 0, out.stderr[-2000:]
     _check_payload(out.stdout, 1)
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float .npy,
+    identically for identical arguments; --full still ends in one line."""
+    import numpy as np
+
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
+             "--model", "llama_test", "--seq-len", "64", "--micro-batch", "2",
+             "--h", "2", "--dump-outputs", str(d), *extra],
+            cwd=REPO, capture_output=True, text=True, timeout=300,
+            env={**os.environ, "BENCH_RUN_DIR": str(tmp_path / "run")},
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert _check_payload(out.stdout, 1)["steps"] == 2
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == set(b) >= {"loss", "weights_sample", "grads_sample"}
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    for name, v in a.items():
+        assert v.dtype in (np.float32, np.float64), name
+        assert v.size > 0 and np.isfinite(v).all(), name
+        assert np.array_equal(v, b[name]), name
+    assert np.abs(a["grads_sample"]).max() > 0
 
 
 def test_bench_two_ranks_cpu():

@@ -4,11 +4,12 @@ curve to gpurun_out/."""
 import json
 import os
 import sys
+from pathlib import Path
 
 import numpy as np
 
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from prime_amd.utils.config import (DilocoConfig, DataSection, MetricsConfig,
                                     ModelConfig, TrainConfig)
 from prime_amd.train import Trainer

@@ -1,5 +1,6 @@
 import sys, time
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 from prime_amd.utils.config import TrainConfig, ModelConfig, DilocoConfig, MetricsConfig
 from prime_amd.train import Trainer
