@@ -25,8 +25,9 @@ from .configs import LlamaConfig, get_config
 class PrimeLinear(nn.Linear):
     """nn.Linear (no bias) routed through layout-tuned hipBLASLt calls
     (ops.tuned_linear): NT forward, NT dX against a per-step cached W^T,
-    NN dW via an LDS-tiled dY transpose. State-dict compatible with
-    nn.Linear."""
+    NN dW via an LDS-tiled dY transpose (the qkv and gate/up projections go
+    through ops.qkv_rope / ops.gateup_swiglu instead, whose backward
+    kernels emit dY^T themselves). State-dict compatible with nn.Linear."""
 
     def forward(self, x):
         return ops.tuned_linear(x, self.weight)
@@ -58,6 +59,20 @@ class Attention(nn.Module):
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
+        if cache is None and pos_dev is None:
+            # training / full-sequence path: projection + RoPE as one op
+            # (strided RoPE reads, packed dqkv + dqkv^T in backward);
+            # composes the plain ops itself when the shape does not tile
+            q, k, v = ops.qkv_rope(x, self.wqkv.weight, cos, sin,
+                                   cfg.n_heads, cfg.n_kv_heads, hd,
+                                   pos_offset=pos)
+            if self.sp_group is not None:
+                from ..parallel.seqpar import ulysses_attention
+
+                o = ulysses_attention(q, k, v, causal=True, group=self.sp_group)
+            else:
+                o = ops.flash_attention(q, k, v, causal=True)
+            return self.wo(o.reshape(B, S, cfg.n_heads * hd))
         qkv = self.wqkv(x)
         q, k, v = qkv.split(
             [cfg.n_heads * hd, cfg.n_kv_heads * hd, cfg.n_kv_heads * hd], dim=-1
@@ -100,7 +115,9 @@ class MLP(nn.Module):
         self.w_down = PrimeLinear(cfg.intermediate, cfg.dim, bias=False)
 
     def forward(self, x):
-        return self.w_down(ops.swiglu(self.w_gateup(x)))
+        # projection + swiglu as one op: its backward emits dgu and dgu^T in
+        # one pass (composes the plain ops when the shape does not tile)
+        return self.w_down(ops.gateup_swiglu(x, self.w_gateup.weight))
 
 
 class Block(nn.Module):

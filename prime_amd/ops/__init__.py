@@ -10,7 +10,14 @@ from .functional import (
     invalidate_wt_cache,
     set_linear_fp8,
     set_linear_tuned,
+    set_direct_wgrad,
+    direct_wgrad_enabled,
     tuned_linear,
+    gateup_swiglu,
+    qkv_rope,
+    qkv_grad_pack,
+    rope_packed_fwd,
+    swiglu_bwd_t,
     attn_decode,
     fused_add_rmsnorm,
     cross_entropy,

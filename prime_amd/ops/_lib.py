@@ -24,6 +24,9 @@ _SIGS = {
     "prime_add_rmsnorm_fwd": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 2 + [ctypes.c_double],
     "prime_add_rmsnorm_bwd": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 3 + [ctypes.c_double],
     "prime_rope": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 4 + [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p],
+    "prime_rope_strided": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 7,
+    "prime_qkv_grad_pack": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 6,
+    "prime_swiglu_bwd_t": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 2,
     "prime_swiglu_fwd": [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 2,
     "prime_swiglu_bwd": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 2,
     "prime_adamw": [ctypes.c_void_p] * 7 + [ctypes.c_int64] + [ctypes.c_double] * 5 + [ctypes.c_int64],

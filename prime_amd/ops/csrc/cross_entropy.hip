@@ -55,8 +55,12 @@ __global__ void ce_fwd_bwd_kernel(const bf16* __restrict__ logits,
       if (tid < stride) {
         const float m2 = red_m[tid + stride], s2 = red_s[tid + stride];
         const float mm = fmaxf(red_m[tid], m2);
-        red_s[tid] = red_s[tid] * __expf(red_m[tid] - mm) + s2 * __expf(m2 - mm);
-        red_m[tid] = mm;
+        // both partials empty (V < 8 * blockDim: threads that saw no
+        // column hold m = -inf, s = 0): -inf - -inf would make a NaN
+        if (mm > -INFINITY) {
+          red_s[tid] = red_s[tid] * __expf(red_m[tid] - mm) + s2 * __expf(m2 - mm);
+          red_m[tid] = mm;
+        }
       }
       __syncthreads();
     }

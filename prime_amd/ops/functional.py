@@ -89,8 +89,15 @@ class _Rope(torch.autograd.Function):
             ctx.cpu = (cos, sin, pos_offset)
             return ref.apply_rope(x, cos, sin, pos_offset)
         ctx.cpu = None
-        x = x.contiguous()
         B, S, H, D = x.shape
+        if pos_dev is None and not x.is_contiguous() and _rope_view_ok(x):
+            # q / k view of a packed qkv buffer: rotate straight out of it
+            # (a dense copy first is a whole extra read + write)
+            y = rope_packed_fwd(x, cos, sin, pos_offset)
+            ctx.save_for_backward(cos, sin)
+            ctx.meta = (B, S, H, D, pos_offset)
+            return y
+        x = x.contiguous()
         y = torch.empty_like(x)
         check(
             lib().prime_rope(
@@ -128,6 +135,60 @@ def apply_rope(x, cos, sin, pos_offset: int = 0, pos_dev=None):
     (optional int32 device scalar) overrides pos_offset at kernel time
     (hipGraph decode)."""
     return _Rope.apply(x, cos, sin, pos_offset, pos_dev)
+
+
+def _rope_view_ok(x: torch.Tensor) -> bool:
+    """[B,S,H,D] view the stride-aware RoPE kernel can read: heads packed
+    inside each token row, one uniform token stride, 8 B aligned rows."""
+    B, S, H, D = x.shape
+    sb, ss, sh, sd = x.stride()
+    return (sd == 1 and sh == D and D % 8 == 0 and ss % 4 == 0
+            and (B == 1 or sb == S * ss) and x.storage_offset() % 4 == 0)
+
+
+def rope_packed_fwd(x, cos, sin, pos_offset: int = 0) -> torch.Tensor:
+    """RoPE forward (no autograd) of a [B,S,H,D] view whose heads sit inside
+    wider packed token rows (q or k inside the qkv GEMM output); returns a
+    contiguous [B,S,H,D] tensor, bit-identical to rotating a dense copy."""
+    if not _rope_view_ok(x):
+        raise NotImplementedError(
+            f"rope_packed_fwd: unsupported view (shape {tuple(x.shape)}, "
+            f"strides {x.stride()})")
+    B, S, H, D = x.shape
+    y = torch.empty(B, S, H, D, device=x.device, dtype=x.dtype)
+    check(
+        lib().prime_rope_strided(
+            stream_of(x), ptr(x), ptr(y), ptr(cos), ptr(sin), B * S * H,
+            H, S, D, x.stride(1), 0, pos_offset,
+        ),
+        "rope_strided",
+    )
+    return y
+
+
+def qkv_grad_pack(dq, dk, dv, cos, sin, pos_offset: int = 0):
+    """Backward of {split qkv, RoPE(q), RoPE(k)} in one pass: dq [B,S,H,D]
+    and dk [B,S,Hkv,D] are gradients of the rotated q/k, dv [B,S,Hkv,D] of
+    v. Returns (dqkv [M,C], dqkv^T [C,M]) with M = B*S, C = (H+2Hkv)*D."""
+    B, S, H, D = dq.shape
+    Hkv = dk.shape[2]
+    M = B * S
+    if D not in (64, 128) or M % 64 != 0:
+        raise NotImplementedError(
+            f"qkv_grad_pack needs head_dim in {{64, 128}} and tokens % 64 == 0 "
+            f"(got head_dim={D}, tokens={M})")
+    dq, dk, dv = dq.contiguous(), dk.contiguous(), dv.contiguous()
+    C = (H + 2 * Hkv) * D
+    dqkv = torch.empty(M, C, device=dq.device, dtype=dq.dtype)
+    dqkvt = torch.empty(C, M, device=dq.device, dtype=dq.dtype)
+    check(
+        lib().prime_qkv_grad_pack(
+            stream_of(dq), ptr(dq), ptr(dk), ptr(dv), ptr(dqkv), ptr(dqkvt),
+            ptr(cos), ptr(sin), M, H, Hkv, S, D, pos_offset,
+        ),
+        "qkv_grad_pack",
+    )
+    return dqkv, dqkvt
 
 
 # ---------------------------------------------------------------- SwiGLU
@@ -169,6 +230,31 @@ class _SwiGLU(torch.autograd.Function):
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     """gu: [..., 2I] (gate ‖ up) -> [..., I] = silu(gate) * up."""
     return _SwiGLU.apply(gu)
+
+
+def swiglu_bwd_t(dout: torch.Tensor, gu: torch.Tensor):
+    """SwiGLU backward (no autograd) that also returns dgu^T for the NN dW
+    GEMM: (dgu [R,2I], dgu^T [2I,R]). One fused pass when R and I tile by
+    64; otherwise the plain backward kernel plus a transpose."""
+    gu = gu.contiguous()
+    dout = dout.contiguous()
+    I = gu.shape[-1] // 2
+    R = gu.numel() // (2 * I)
+    dgu = torch.empty_like(gu)
+    if R % 64 == 0 and I % 64 == 0 and R > 0:
+        dgut = torch.empty(2 * I, R, device=gu.device, dtype=gu.dtype)
+        check(
+            lib().prime_swiglu_bwd_t(stream_of(gu), ptr(dout), ptr(gu),
+                                     ptr(dgu), ptr(dgut), R, I),
+            "swiglu_bwd_t",
+        )
+        return dgu, dgut
+    if I % 8 != 0:
+        raise NotImplementedError(
+            f"swiglu kernel needs intermediate dim % 8 == 0 (got {I})")
+    check(lib().prime_swiglu_bwd(stream_of(gu), ptr(dout), ptr(gu), ptr(dgu), R, I),
+          "swiglu_bwd")
+    return dgu, dgu.view(R, 2 * I).t().contiguous()
 
 
 # ------------------------------------------------------- flash attention
@@ -434,9 +520,85 @@ def _transpose_quant_fp8(x2: torch.Tensor, site: tuple, e5m2: bool = False):
     return xt8, st["sinv"]
 
 
-def _compute_dw(x2, w, dy2):
+# Direct wgrad: a FlatParamSpace makes p.grad a view of its flat gradient,
+# so autograd's accumulate turns every dW into {GEMM writes a temporary;
+# grad += temporary} on top of the per-step zero fill — three writes of a
+# weight-sized tensor where one is needed. A space registers the grad view
+# of each untied PrimeLinear weight here; while a slot is armed (between
+# the space's zero_grad() and the weight's first gradient of the step) the
+# dW GEMM writes straight into the view and backward hands autograd None.
+# Later gradients in the same step (grad accumulation) go through autograd
+# as before, so accumulated values do not change.
+_DIRECT_WGRAD = False
+# (data_ptr, N, K) -> [grad_view, armed, owner_ref, autograd_pending]
+_WGRAD_SLOTS: dict = {}
+
+
+def set_direct_wgrad(on: bool) -> None:
+    """Let dW GEMMs write into registered flat-gradient views (Trainer:
+    CUDA + FlatParamSpace; bare modules keep autograd's accumulate)."""
+    global _DIRECT_WGRAD
+    _DIRECT_WGRAD = bool(on)
+
+
+def direct_wgrad_enabled() -> bool:
+    return _DIRECT_WGRAD
+
+
+def register_wgrad_slot(w: torch.Tensor, grad_view: torch.Tensor, owner):
+    """Called by FlatParamSpace; `owner` is a weakref to the space. Returns
+    the slot (the space arms/disarms it by setting slot[1]; slot[3] asks
+    it to zero the view instead of arming at its next zero_grad())."""
+    slot = [grad_view, False, owner, False]
+    _WGRAD_SLOTS[(w.data_ptr(), *w.shape)] = slot
+    return slot
+
+
+def unregister_wgrad_slots(owner) -> None:
+    for k in [k for k, s in _WGRAD_SLOTS.items() if s[2] is owner]:
+        del _WGRAD_SLOTS[k]
+
+
+def _wgrad_take(w: torch.Tensor):
+    """The flat-gradient view to write w's dW into, if this is the first
+    gradient of the step for a registered weight; else None."""
+    if not _WGRAD_SLOTS:
+        return None
+    slot = _WGRAD_SLOTS.get((w.data_ptr(), *w.shape))
+    if slot is None or not slot[1]:
+        return None
+    if slot[2]() is None:  # owning space is gone
+        del _WGRAD_SLOTS[(w.data_ptr(), *w.shape)]
+        return None
+    slot[1] = False
+    return slot[0]
+
+
+def _wgrad_release(w: torch.Tensor) -> None:
+    """w's gradient will reach its grad view through autograd's accumulate
+    (a forward that does not lead to _compute_dw): give the view the zero
+    it expects — now if the step has started, else at its zero_grad()."""
+    if not _WGRAD_SLOTS:
+        return
+    out = _wgrad_take(w)
+    if out is not None:
+        out.zero_()
+    elif torch.is_grad_enabled():
+        slot = _WGRAD_SLOTS.get((w.data_ptr(), *w.shape))
+        if slot is not None:
+            slot[3] = True
+
+
+def _compute_dw(x2, w, dy2, dyt=None):
+    """dW = dY^T @ X. `dyt` is dY^T when the producer of dY already emitted
+    it (fused swiglu / qkv-pack backward). Returns None when the GEMM wrote
+    the registered flat-gradient view directly."""
     N, K = w.shape
     M = x2.shape[0]
+    out = _wgrad_take(w)
+    if out is not None and not (out.dtype == x2.dtype == dy2.dtype):
+        out.zero_()  # mixed dtypes: leave the accumulate to autograd
+        out = None
     if N % 128 == 0 and M % 64 == 0 and M >= 4096:
         if (_LINEAR_FP8_WGRAD and K % 128 == 0 and M % 16 == 0
                 and x2.dtype == torch.bfloat16):
@@ -446,10 +608,17 @@ def _compute_dw(x2, w, dy2):
                 dy2, ("dyT", w.data_ptr(), *w.shape), e5m2=True)
             g = torch._scaled_mm(xt8, dyt8.t(), scale_a=xtinv,
                                  scale_b=dytinv, out_dtype=x2.dtype)
-            return transpose_bshd(g.view(1, K, N // 128, 128)).view(N, K)
-        dyt = transpose_bshd(dy2.view(1, M, N // 128, 128)).view(N, M)
-        return torch.mm(dyt, x2)
-    return torch.mm(dy2.t(), x2)
+            dw = transpose_bshd(g.view(1, K, N // 128, 128)).view(N, K)
+            if out is not None:
+                out.copy_(dw)
+                return None
+            return dw
+        if dyt is None:
+            dyt = transpose_bshd(dy2.view(1, M, N // 128, 128)).view(N, M)
+        dw = torch.mm(dyt, x2, out=out)
+    else:
+        dw = torch.mm(dyt if dyt is not None else dy2.t(), x2, out=out)
+    return None if out is not None else dw
 
 
 def _linear_backward(x2, w, dy):
@@ -641,10 +810,117 @@ def tuned_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     skinny decode GEMMs (M < 1024) keep the F.linear dispatch, which
     measured faster there (decode A/B: 2881 vs 2688 graph tok/s)."""
     if not _is_hip(x) or x.numel() // x.shape[-1] < 1024:
+        _wgrad_release(w)  # dW will come through autograd's accumulate
         return torch.nn.functional.linear(x, w)
     if _LINEAR_FP8 and x.shape[-1] % 16 == 0 and w.shape[0] % 16 == 0:
         return _Fp8Linear.apply(x, w)
     return _TunedLinear.apply(x, w)
+
+
+# ------------------------------------- fused projection + layout producers
+# The gate/up and qkv projections feed kernels of ours on both sides, so
+# the backward of those kernels can emit dY^T (the NN dW GEMM's operand)
+# while it still holds dY in registers, instead of a separate transpose
+# pass re-reading what was just written. The GEMMs see the same operands
+# as tuned_linear's, so results match the composed ops bit for bit.
+def _fused_layout_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """Same conditions under which _compute_dw takes its dY^T branch, on
+    the plain bf16 tuned path (Trainer, non-FSDP, fp8 off)."""
+    if not (_LINEAR_TUNED and not _LINEAR_FP8 and _is_hip(x)):
+        return False
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or w.dim() != 2:
+        return False
+    M = x.numel() // x.shape[-1]
+    return w.shape[0] % 128 == 0 and M % 64 == 0 and M >= 4096
+
+
+def _dx_of(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    wt = _wt_of(w) if _LINEAR_TUNED else None
+    return torch.matmul(dy2, wt.t()) if wt is not None else torch.matmul(dy2, w)
+
+
+class _GateUpSwiGLU(torch.autograd.Function):
+    """swiglu(x @ W_gateup^T) as one node; saves {x, w, gu} like the
+    composed ops. Backward: one kernel writes dgu and dgu^T."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        x2 = x.reshape(-1, x.shape[-1])
+        gu = torch.matmul(x2, w.t())
+        I = w.shape[0] // 2
+        out = torch.empty(x2.shape[0], I, device=x.device, dtype=x.dtype)
+        check(lib().prime_swiglu_fwd(stream_of(gu), ptr(gu), ptr(out),
+                                     x2.shape[0], I), "swiglu_fwd")
+        ctx.save_for_backward(x2, w, gu)
+        ctx.xshape = x.shape
+        return out.view(*x.shape[:-1], I)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, w, gu = ctx.saved_tensors
+        dgu, dgut = swiglu_bwd_t(dout.reshape(-1, dout.shape[-1]), gu)
+        dx = _dx_of(dgu, w)
+        return dx.view(ctx.xshape), _compute_dw(x2, w, dgu, dyt=dgut)
+
+
+def gateup_swiglu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """silu(gate) * up of the packed projection x @ w^T, w: [2I, K]."""
+    if _fused_layout_ok(x, w):
+        return _GateUpSwiGLU.apply(x, w)
+    return swiglu(tuned_linear(x, w))
+
+
+class _QkvRope(torch.autograd.Function):
+    """(RoPE(q), RoPE(k), v) of the packed projection x @ W_qkv^T. q and k
+    are rotated straight out of the GEMM output; v is a view of it.
+    Backward packs dq/dk/dv into dqkv and dqkv^T in one kernel."""
+
+    @staticmethod
+    def forward(ctx, x, w, cos, sin, H, Hkv, D, pos_offset):
+        B, S, K = x.shape
+        x2 = x.reshape(-1, K)
+        qkv = torch.matmul(x2, w.t()).view(B, S, -1)
+        q = rope_packed_fwd(qkv[..., : H * D].view(B, S, H, D), cos, sin,
+                            pos_offset)
+        k = rope_packed_fwd(
+            qkv[..., H * D : (H + Hkv) * D].view(B, S, Hkv, D), cos, sin,
+            pos_offset)
+        v = qkv[..., (H + Hkv) * D :].view(B, S, Hkv, D)
+        ctx.save_for_backward(x2, w, cos, sin)
+        ctx.meta = (B, S, K, H, Hkv, D, pos_offset)
+        return q, k, v
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        x2, w, cos, sin = ctx.saved_tensors
+        B, S, K, H, Hkv, D, off = ctx.meta
+        # missing grads become dense zeros
+        if dq is None:
+            dq = x2.new_zeros(B, S, H, D)
+        if dk is None:
+            dk = x2.new_zeros(B, S, Hkv, D)
+        if dv is None:
+            dv = x2.new_zeros(B, S, Hkv, D)
+        dqkv, dqkvt = qkv_grad_pack(dq, dk, dv, cos, sin, off)
+        dx = _dx_of(dqkv, w)
+        return (dx.view(B, S, K), _compute_dw(x2, w, dqkv, dyt=dqkvt),
+                None, None, None, None, None, None)
+
+
+def qkv_rope(x, w, cos, sin, n_heads: int, n_kv_heads: int, head_dim: int,
+             pos_offset: int = 0):
+    """x [B,S,K] @ w^T -> (RoPE(q) [B,S,H,D], RoPE(k) [B,S,Hkv,D],
+    v [B,S,Hkv,D]); w: [(H+2Hkv)*D, K]."""
+    H, Hkv, D = n_heads, n_kv_heads, head_dim
+    if (x.dim() == 3 and D in (64, 128) and w.shape[0] == (H + 2 * Hkv) * D
+            and _fused_layout_ok(x, w)):
+        return _QkvRope.apply(x, w, cos, sin, H, Hkv, D, pos_offset)
+    B, S = x.shape[0], x.shape[1]
+    qkv = tuned_linear(x, w)
+    q, k, v = qkv.split([H * D, Hkv * D, Hkv * D], dim=-1)
+    q = apply_rope(q.view(B, S, H, D), cos, sin, pos_offset=pos_offset)
+    k = apply_rope(k.view(B, S, Hkv, D), cos, sin, pos_offset=pos_offset)
+    return q, k, v.view(B, S, Hkv, D)
 
 
 # ------------------------------------------------- raw (non-autograd) ops

@@ -12,6 +12,7 @@ aligned). Consequences, all MI355X-deliberate:
 """
 from __future__ import annotations
 
+import weakref
 from typing import Iterator
 
 import torch
@@ -64,17 +65,94 @@ class FlatParamSpace:
             p.grad = self.flat_grad[o : o + k].view(shp)
         self.master32 = self.flat_w.float()
         self._sq = None
+        self._register_direct_wgrad()
+
+    # ------------------------------------------------------ direct wgrad
+    def _register_direct_wgrad(self) -> None:
+        """Untied 2-D PrimeLinear weights get their dW written by the GEMM
+        straight into flat_grad (ops.functional, 'Direct wgrad'), so their
+        ranges need neither the per-step zero fill nor autograd's
+        `grad += dW`. direct_ranges / zero_ranges partition
+        [0, numel_padded): zero_grad() fills only the latter."""
+        from ..models.llama import PrimeLinear
+
+        uses: dict[int, int] = {}
+        for _, p in self.module.named_parameters(remove_duplicate=False):
+            uses[id(p)] = uses.get(id(p), 0) + 1
+        name_of = {id(p): n for n, p in self.params}
+        direct: list[tuple[int, int, str]] = []
+        for m in self.module.modules():
+            if not isinstance(m, PrimeLinear) or m.bias is not None:
+                continue
+            p = m.weight
+            n = name_of.get(id(p))
+            if n is None or p.dim() != 2 or uses[id(p)] != 1:
+                continue  # frozen or tied (shared with another module)
+            o, k, _ = self.offsets[n]
+            direct.append((o, o + k, n))
+        direct.sort()
+        self.direct_ranges = [(a, b) for a, b, _ in direct]
+        self.zero_ranges: list[tuple[int, int]] = []
+        cur = 0
+        for a, b in self.direct_ranges:
+            if a > cur:
+                self.zero_ranges.append((cur, a))
+            cur = b
+        if cur < self.numel_padded:
+            self.zero_ranges.append((cur, self.numel_padded))
+        self._slots = []
+        self._direct_step = False
+        if self.device.type != "cuda":
+            return  # CPU linears never reach the dW GEMM hook
+        self._owner = weakref.ref(self)
+        params = dict(self.params)
+        for a, b, n in direct:
+            p = params[n]
+            self._slots.append(ops.functional.register_wgrad_slot(
+                p, self.flat_grad[a:b].view(p.shape), self._owner))
+        weakref.finalize(self, ops.functional.unregister_wgrad_slots,
+                         self._owner)
 
     def zero_grad(self) -> None:
-        self.flat_grad.zero_()
+        """Start a step. With direct wgrad on, registered weight ranges are
+        left alone (their first dW of the step overwrites them); call
+        finalize_grads() before reading flat_grad."""
+        if not (self._slots and ops.direct_wgrad_enabled()):
+            for s in self._slots:
+                s[1] = s[3] = False
+            self._direct_step = False
+            self.flat_grad.zero_()
+            return
+        for a, b in self.zero_ranges:
+            self.flat_grad[a:b].zero_()
+        for s in self._slots:
+            if s[3]:  # a forward already routed this dW through autograd
+                s[0].zero_()
+                s[1] = s[3] = False
+            else:
+                s[1] = True
+        self._direct_step = True
+
+    def finalize_grads(self) -> None:
+        """Before flat_grad is consumed: a registered weight that received
+        no gradient this step still holds last step's values — zero it."""
+        if not self._direct_step:
+            return
+        for s in self._slots:
+            if s[1]:
+                s[0].zero_()
+                s[1] = False
+        self._direct_step = False
 
     def grad_views(self) -> Iterator[torch.Tensor]:
+        self.finalize_grads()
         for n, _ in self.params:
             o, k, shp = self.offsets[n]
             yield self.flat_grad[o : o + k].view(shp)
 
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         """Global-norm clip on the flat grad (single fused pass)."""
+        self.finalize_grads()
         norm = self.flat_grad.float().norm(2)
         scale = (max_norm / (norm + 1e-6)).clamp(max=1.0)
         self.flat_grad.mul_(scale.to(self.flat_grad.dtype))
@@ -87,6 +165,7 @@ class FlatParamSpace:
         if self._sq is None:
             self._sq = torch.zeros(1, device=self.device, dtype=torch.float32)
         self._sq.zero_()
+        self.finalize_grads()
         ops.grad_sqnorm(self.flat_grad, self._sq)
         return (max_norm / (self._sq.sqrt() + 1e-6)).clamp(max=1.0)
 

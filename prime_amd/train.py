@@ -134,6 +134,9 @@ class Trainer:
         from . import ops as _ops
 
         _ops.set_linear_tuned(self.device.type == "cuda" and not self.fsdp)
+        # dW GEMMs write straight into the flat gradient (FlatParamSpace
+        # only: the FSDP space reduce-scatters per-unit grads instead)
+        _ops.set_direct_wgrad(self.device.type == "cuda" and not self.fsdp)
         _ops.set_linear_fp8(cfg.model.fp8 and self.device.type == "cuda",
                             dgrad=cfg.model.fp8_dgrad,
                             wgrad=cfg.model.fp8_wgrad)
@@ -251,6 +254,7 @@ class Trainer:
         if self.fsdp:
             self.flat.finalize_grads()  # sharded units were reduce-scattered in bwd
         else:
+            self.flat.finalize_grads()  # direct wgrad: zero untouched weights
             self.mesh.local_allreduce_grad(self.flat.flat_grad)
         gscale = None
         if cfg.optim.grad_clip > 0:
