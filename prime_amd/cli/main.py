@@ -606,6 +606,12 @@ def prepare_data(
     shard_tokens: int = typer.Option(512 * 1024 * 1024,
                                      help="tokens per output shard"),
     workers: int = typer.Option(0, help="parallel tokenizer processes"),
+    eos_id: Optional[int] = typer.Option(
+        None, "--eos-id", help="append this token id at the end of every "
+        "input file (document boundary for data.doc_mask_eos_id)"),
+    doc_separator: Optional[str] = typer.Option(
+        None, "--doc-separator", help="with --eos-id: a line whose stripped "
+        "text equals this is dropped and replaced by the EOS token"),
     json_out: bool = typer.Option(False, "--json"),
 ):
     """Tokenize text into token shards for the token_file dataloader.
@@ -617,9 +623,13 @@ def prepare_data(
     try:
         res = prepare_corpus(inputs, out, tokenizer,
                              vocab_threshold=vocab_threshold,
-                             shard_tokens=shard_tokens, workers=workers)
+                             shard_tokens=shard_tokens, workers=workers,
+                             eos_id=eos_id, doc_separator=doc_separator)
     except FileNotFoundError as e:
         secho(f"input not found: {e}", fg="red")
+        raise typer.Exit(1)
+    except ValueError as e:
+        secho(str(e), fg="red")
         raise typer.Exit(1)
     if json_out:
         emit_json(res)
@@ -637,6 +647,9 @@ def eval_cmd(
     batches: int = typer.Option(10),
     micro_batch: int = typer.Option(4),
     checkpoint: Optional[str] = typer.Option(None, help="checkpoint dir"),
+    doc_mask_eos_id: Optional[int] = typer.Option(
+        None, "--doc-mask-eos-id", min=0,
+        help="attend within documents only; a document ends at this token id"),
     json_out: bool = typer.Option(False, "--json"),
 ):
     """Held-out loss / perplexity (reference: prime eval surface)."""
@@ -664,7 +677,8 @@ def eval_cmd(
         flat.load_flat_(payload["tensors"]["master32"].to(dev))
     dc = DataConfig(kind="token_file" if data else "synthetic", path=data,
                     seq_len=seq_len, micro_batch_size=micro_batch)
-    res = evaluate_perplexity(m, dc, n_batches=batches, device=dev)
+    res = evaluate_perplexity(m, dc, n_batches=batches, device=dev,
+                              doc_mask_eos_id=doc_mask_eos_id)
     if json_out:
         typer.echo(json.dumps(res))
     else:

@@ -35,6 +35,32 @@ def iter_blocks(paths: list[Path], block_bytes: int = _BLOCK_BYTES) -> Iterator[
                 yield "".join(buf)
 
 
+def iter_segments(paths: list[Path], separator: str | None,
+                  block_bytes: int = _BLOCK_BYTES) -> Iterator[str | None]:
+    """iter_blocks with document boundaries: yields text blocks, and None
+    where an EOS token belongs — at the end of every file and, with a
+    separator, in place of every line whose stripped text equals it."""
+    for p in paths:
+        with open(p, encoding="utf-8", errors="replace") as fh:
+            buf: list[str] = []
+            size = 0
+            for line in fh:
+                if separator is not None and line.strip() == separator:
+                    if buf:
+                        yield "".join(buf)
+                        buf, size = [], 0
+                    yield None
+                    continue
+                buf.append(line)
+                size += len(line)
+                if size >= block_bytes:
+                    yield "".join(buf)
+                    buf, size = [], 0
+            if buf:
+                yield "".join(buf)
+        yield None
+
+
 _TOK = None
 
 
@@ -45,7 +71,9 @@ def _worker_init(tokenizer_path: str) -> None:
     _TOK = load_tokenizer(tokenizer_path)
 
 
-def _encode_block(text: str) -> np.ndarray:
+def _encode_block(text: str | None, eos_id: int | None = None) -> np.ndarray:
+    if text is None:  # document boundary (iter_segments)
+        return np.asarray([eos_id], dtype=np.int64)
     return np.asarray(_TOK.encode(text).ids, dtype=np.int64)
 
 
@@ -104,9 +132,23 @@ def prepare_corpus(
     vocab_threshold: int = 65535,
     shard_tokens: int = 512 * 1024 * 1024,
     workers: int = 0,
+    eos_id: int | None = None,
+    doc_separator: str | None = None,
 ) -> dict:
-    """Tokenize text files into token shards. Returns a summary dict."""
+    """Tokenize text files into token shards. Returns a summary dict.
+
+    eos_id: append this token id at the end of every input file and, with
+    doc_separator, at every line whose stripped text equals it (that line
+    is dropped) — the boundaries `data.doc_mask_eos_id` acts on. Without
+    eos_id the output is unchanged."""
+    import functools
+
     from ..utils.tokenizer import load_tokenizer
+
+    if doc_separator is not None and eos_id is None:
+        raise ValueError("doc_separator needs eos_id")
+    if eos_id is not None and eos_id < 0:
+        raise ValueError("eos_id must be >= 0")
 
     paths = [Path(p) for p in inputs]
     for p in paths:
@@ -114,7 +156,14 @@ def prepare_corpus(
             raise FileNotFoundError(p)
     vocab = load_tokenizer(tokenizer_path).get_vocab_size()
     dtype = np.uint16 if vocab <= vocab_threshold else np.uint32
+    if eos_id is not None and eos_id > np.iinfo(dtype).max:
+        raise ValueError(f"eos_id {eos_id} does not fit {np.dtype(dtype).name}")
     writer = ShardWriter(Path(out), dtype, shard_tokens)
+    if eos_id is None:
+        items, encode = iter_blocks(paths), _encode_block
+    else:
+        items = iter_segments(paths, doc_separator)
+        encode = functools.partial(_encode_block, eos_id=eos_id)
 
     if workers and workers > 1:
         import multiprocessing as mp
@@ -122,12 +171,12 @@ def prepare_corpus(
         ctx = mp.get_context("spawn")
         with ctx.Pool(workers, initializer=_worker_init,
                       initargs=(tokenizer_path,)) as pool:
-            for ids in pool.imap(_encode_block, iter_blocks(paths), chunksize=1):
+            for ids in pool.imap(encode, items, chunksize=1):
                 writer.write(ids)
     else:
         _worker_init(tokenizer_path)
-        for block in iter_blocks(paths):
-            writer.write(_encode_block(block))
+        for block in items:
+            writer.write(encode(block))
     shards = writer.close()
     return {
         "tokens": writer.total,

@@ -55,10 +55,18 @@ class Attention(nn.Module):
     # over the full context via two all-to-alls (parallel/seqpar.py)
     sp_group = None
 
-    def forward(self, x, cos, sin, cache=None, pos: int = 0, pos_dev=None):
+    def forward(self, x, cos, sin, cache=None, pos: int = 0, pos_dev=None,
+                doc_start=None):
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
+        if doc_start is not None and (cache is not None or pos_dev is not None):
+            raise ValueError("doc_start (document mask) is a full-sequence "
+                             "training/eval option; the KV-cache and decode "
+                             "paths do not take it")
+        if doc_start is not None and self.sp_group is not None:
+            raise ValueError("doc_start is not supported with sequence "
+                             "parallelism")
         if cache is None and pos_dev is None:
             # training / full-sequence path: projection + RoPE as one op
             # (strided RoPE reads, packed dqkv + dqkv^T in backward);
@@ -71,7 +79,8 @@ class Attention(nn.Module):
 
                 o = ulysses_attention(q, k, v, causal=True, group=self.sp_group)
             else:
-                o = ops.flash_attention(q, k, v, causal=True)
+                o = ops.flash_attention(q, k, v, causal=True,
+                                        doc_start=doc_start)
             return self.wo(o.reshape(B, S, cfg.n_heads * hd))
         qkv = self.wqkv(x)
         q, k, v = qkv.split(
@@ -133,10 +142,12 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, res, cos, sin, cache=None, pos: int = 0, pos_dev=None):
+    def forward(self, x, res, cos, sin, cache=None, pos: int = 0, pos_dev=None,
+                doc_start=None):
         y, s = ops.fused_add_rmsnorm(x, res, self.attn_norm.weight,
                                      self.attn_norm.eps)
-        a = self.attn(y, cos, sin, cache=cache, pos=pos, pos_dev=pos_dev)
+        a = self.attn(y, cos, sin, cache=cache, pos=pos, pos_dev=pos_dev,
+                      doc_start=doc_start)
         y2, s2 = ops.fused_add_rmsnorm(a, s, self.mlp_norm.weight,
                                        self.mlp_norm.eps)
         return self.mlp(y2), s2
@@ -181,10 +192,17 @@ class Llama(nn.Module):
         self.rope_sin = sin
 
     def forward(self, tokens: torch.Tensor, caches=None, pos: int = 0,
-                pos_dev=None) -> torch.Tensor:
+                pos_dev=None, doc_start=None) -> torch.Tensor:
         """tokens [B,S] -> hidden states [B,S,dim] (pre-lm_head).
         caches: optional per-layer (k,v) KV caches for inference; pos_dev:
-        device-scalar position dict for hipGraph-captured decode."""
+        device-scalar position dict for hipGraph-captured decode.
+        doc_start: optional int32 [B,S] document mask (ops.doc_starts) for
+        packed sequences, shared by every layer. Positions are NOT reset per
+        document: RoPE is relative, so attention within a document does not
+        depend on the document's offset."""
+        if doc_start is not None and (caches or pos_dev is not None):
+            raise ValueError("doc_start cannot be combined with KV caches or "
+                             "decode positions")
         x = self.tok_embeddings(tokens)
         res = None
         if pos == 0 and self.sp_pos_offset:
@@ -192,17 +210,24 @@ class Llama(nn.Module):
         cos, sin = self.rope_cos, self.rope_sin
         for i, blk in enumerate(self.layers):
             if self.activation_checkpointing and self.training:
-                x, res = checkpoint(blk, x, res, cos, sin, use_reentrant=False)
+                if doc_start is None:
+                    x, res = checkpoint(blk, x, res, cos, sin, use_reentrant=False)
+                else:
+                    x, res = checkpoint(blk, x, res, cos, sin,
+                                        use_reentrant=False, doc_start=doc_start)
             else:
                 x, res = blk(x, res, cos, sin,
                              cache=caches[i] if caches else None, pos=pos,
-                             pos_dev=pos_dev)
+                             pos_dev=pos_dev, doc_start=doc_start)
         y, _ = ops.fused_add_rmsnorm(x, res, self.norm.weight, self.norm.eps)
         return y
 
-    def loss(self, tokens: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-        """Fused lm_head + cross-entropy. tokens/targets: [B,S]."""
-        h = self.forward(tokens)
+    def loss(self, tokens: torch.Tensor, targets: torch.Tensor,
+             doc_start=None) -> torch.Tensor:
+        """Fused lm_head + cross-entropy. tokens/targets: [B,S]. Targets are
+        untouched by doc_start: a document's first token is still predicted
+        from the preceding EOS."""
+        h = self.forward(tokens, doc_start=doc_start)
         logits = self.lm_head(h).flatten(0, 1)
         return ops.cross_entropy(logits, targets.flatten(), ignore_index=-100)
 

@@ -22,6 +22,7 @@ from .functional import (
     fused_add_rmsnorm,
     cross_entropy,
     dequant_int8,
+    doc_starts,
     flash_attention,
     fused_adamw,
     grad_sqnorm,
@@ -43,6 +44,7 @@ __all__ = [
     "fused_add_rmsnorm",
     "cross_entropy",
     "dequant_int8",
+    "doc_starts",
     "flash_attention",
     "fused_adamw",
     "grad_sqnorm",

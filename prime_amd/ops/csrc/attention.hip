@@ -113,16 +113,31 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// ---- document mask ------------------------------------------------------
+// doc_start[B][S] int32: index of the first token of the document that
+// token i belongs to (0 <= doc_start[i] <= i, non-decreasing in i). Query
+// i sees key j iff doc_start[i] <= j <= i. The dK/dV kernel uses the
+// mirror array doc_end[B][S] (exclusive end of key j's document): query i
+// sees key j iff j <= i < doc_end[j]. Every loop bound taken from either
+// array goes through doc_clamp, so an out-of-contract array can give wrong
+// numbers but never an out-of-range tile address.
+__device__ __forceinline__ int doc_clamp(int v, int hi) {
+  return v < 0 ? 0 : (v > hi ? hi : v);
+}
+
 // ---------------------------------------------------------------- forward
 // Q[B,S,H,D] (strided), K[B,S,Hkv,D] (strided), Vt[B,Hkv,D,S] (contiguous)
 // -> O[B,S,H,D] (contiguous), lse[B,S,H] fp32.
-template <int D, int NW>  // NW waves x 16 q-rows per block
+// DOC: document mask (see "document mask" above doc_clamp) — a separate
+// instantiation; DOC=false compiles to the code it was before the mask.
+template <int D, int NW, bool DOC = false>  // NW waves x 16 q-rows per block
 __global__ __launch_bounds__(512) void flash_fwd_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ Vt, bf16* __restrict__ O, float* __restrict__ lse,
     int B, int H, int Hkv, int S, float scale, int causal,
     int64_t sqb, int64_t sqs, int64_t sqh,
-    int64_t skb, int64_t sks, int64_t skh) {
+    int64_t skb, int64_t sks, int64_t skh,
+    const int* __restrict__ doc) {
   constexpr int DS = D / 32;
   constexpr int DT = D / 16;
   constexpr int QT = NW * 16;  // q rows per block
@@ -161,12 +176,24 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
   for (int dt = 0; dt < DT; ++dt) o_acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int kv_end = causal ? (qt * QT + QT) : S;
-  for (int kv = 0; kv < kv_end; kv += 64) {
+  // DOC: the block's first row has its smallest doc_start, so the k/v loop
+  // starts at that tile (block-uniform: all waves co-stage); a wave whose
+  // own first row starts later skips the leading tiles' compute
+  int kv_begin = 0, my_kv_begin = 0, row_ds[4];
+  if (DOC) {
+    const int* doc_b = doc + (int64_t)b * S;
+    kv_begin = doc_clamp(doc_b[qt * QT], qt * QT) & ~63;
+    my_kv_begin = doc_clamp(doc_b[q0], q0) & ~63;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) row_ds[r] = doc_b[q0 + lg * 4 + r];
+  }
+  for (int kv = kv_begin; kv < kv_end; kv += 64) {
     __syncthreads();  // all waves done reading the previous tile
     stage_tile<64, D, NW * 64>(Kb + (int64_t)kv * sks, sks, k_lds, threadIdx.x);
     // Vt tile: rows d (stride S), cols k in [kv, kv+64)
     stage_tile<D, 64, NW * 64>(Vtb + kv, S, vt_lds, threadIdx.x);
     __syncthreads();  // staged (syncthreads drains vmcnt)
+    if (DOC && kv < my_kv_begin) continue;  // before this wave's documents
 
     // ---- S = scale * Q K^T
     f32x4 s[4];
@@ -190,6 +217,7 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
       for (int sub = 0; sub < 4; ++sub) {
         float v = s[sub][r] * scale;
         if (causal && (kv + sub * 16 + li) > qg) v = NEG_INF;
+        if (DOC && (kv + sub * 16 + li) < row_ds[r]) v = NEG_INF;
         s[sub][r] = v;
         tmax = fmaxf(tmax, v);
       }
@@ -216,7 +244,11 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
       float psum = 0.f;
 #pragma unroll
       for (int sub = 0; sub < 4; ++sub) {
-        const float p = __expf(s[sub][r] - mnew);
+        // DOC: a row can meet a tile that lies wholly before its document
+        // (m, mnew and s all NEG_INF): exp(0) = 1 there, so masked scores
+        // are zeroed explicitly
+        const float p = (DOC && s[sub][r] <= NEG_INF)
+                            ? 0.f : __expf(s[sub][r] - mnew);
         s[sub][r] = p;
         psum += p;
       }
@@ -307,13 +339,14 @@ __device__ __forceinline__ void permlane32_swap(unsigned& a, unsigned& b) {
 // (guide T4: __syncthreads' vmcnt(0) drain waits on the JUST-issued
 // stage; with 2 tiles of lookahead the boundary only needs the oldest
 // in-flight tile, so vmcnt(4) leaves the newest 4 loads flying)
-template <int D, int FLAGS>
+template <int D, int FLAGS, bool DOC = false>
 __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ Vt, bf16* __restrict__ O, float* __restrict__ lse,
     int B, int H, int Hkv, int S, float scale, int causal,
     int64_t sqb, int64_t sqs, int64_t sqh,
-    int64_t skb, int64_t sks, int64_t skh) {
+    int64_t skb, int64_t sks, int64_t skh,
+    const int* __restrict__ doc) {
   constexpr int DSL = D / 16;   // 16-wide d slices for the K dim
   constexpr int DT32 = D / 32;  // 32-wide output d tiles
   const int n_qt = S / 256;
@@ -367,16 +400,29 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
   // per-wave causal clip: this wave's rows end at q0w+31, so tiles past
   // q0w+32 are fully masked — skip their compute (they still stage+sync)
   const int my_kv_end = causal ? (q0w + 32) : S;
-  stage_tile<64, D, 512>(Kb, sks, k_lds[0], threadIdx.x);
-  stage_tile<D, 64, 512>(Vtb, S, vt_lds[0], threadIdx.x);
+  // DOC: block-uniform loop start at the tile of the block's smallest
+  // doc_start (its first row's); per-wave start for the compute skip; the
+  // lane's own row start for the element mask, which only tiles that
+  // begin before the wave's LAST row's start (its largest) need. The
+  // prologue stages and the prefetch distance are relative to kv_begin.
+  int kv_begin = 0, my_kv_begin = 0, my_ds = 0, my_ds_last = 0;
+  if (DOC) {
+    const int* doc_b = doc + (int64_t)b * S;
+    kv_begin = doc_clamp(doc_b[qt * 256], qt * 256) & ~63;
+    my_kv_begin = doc_clamp(doc_b[q0w], q0w) & ~63;
+    my_ds = doc_b[q0w + lo];
+    my_ds_last = doc_b[q0w + 31];
+  }
+  stage_tile<64, D, 512>(Kb + (int64_t)kv_begin * sks, sks, k_lds[0], threadIdx.x);
+  stage_tile<D, 64, 512>(Vtb + kv_begin, S, vt_lds[0], threadIdx.x);
   if (FLAGS & 4) {  // 2-deep prologue
-    if (64 < kv_end) {
-      stage_tile<64, D, 512>(Kb + (int64_t)64 * sks, sks, k_lds[1], threadIdx.x);
-      stage_tile<D, 64, 512>(Vtb + 64, S, vt_lds[1], threadIdx.x);
+    if (kv_begin + 64 < kv_end) {
+      stage_tile<64, D, 512>(Kb + (int64_t)(kv_begin + 64) * sks, sks, k_lds[1], threadIdx.x);
+      stage_tile<D, 64, 512>(Vtb + kv_begin + 64, S, vt_lds[1], threadIdx.x);
     }
   }
   int idx = 0;
-  for (int kv = 0, kt = 0; kv < kv_end; kv += 64, ++kt) {
+  for (int kv = kv_begin, kt = 0; kv < kv_end; kv += 64, ++kt) {
     idx = kt % NBUF;
     if (FLAGS & 4) {
       // tile kv's stages are >=1 full tile old: only the newest tile's
@@ -403,6 +449,7 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
       }
     }
     if (kv >= my_kv_end) continue;  // fully-masked tile for this wave
+    if (DOC && kv < my_kv_begin) continue;  // before this wave's documents
 
     // ---- St = (K q^T): two 32x32 C tiles over the 64-key block
     f32x16 st[2];
@@ -421,6 +468,18 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
     // ---- online softmax: st[t][r] is k = kv + t*32 + crow(r,hi) for
     // q row q0w+lo; lane pair (l, l^32) splits the row's 64 scores
     float tmax = NEG_INF;
+    if (DOC && kv < my_ds_last) {  // wave-uniform: a boundary tile
+      // a row still wholly masked keeps m_run = NEG_INF through the
+      // per-wave rescale below (alpha = exp(0) = 1 on o = l = 0) and
+      // p = 0 through the <= NEG_INF guard, so nothing leaks
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kg = kv + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          if (kg < my_ds) st[t][r] = NEG_INF;
+        }
+    }
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -533,7 +592,7 @@ __global__ void attn_delta_kernel(const bf16* __restrict__ dO,
 // dPt = V·dO^T give lane-local q-rows (q = lane&31), so lse/delta are one
 // scalar per lane and dS never touches LDS — it is packed straight into
 // the dQ-accumulation A-fragments with cvt_pk + permlane32_swap.
-template <int D, int FLAGS>
+template <int D, int FLAGS, bool DOC = false>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ Kt,
@@ -542,7 +601,8 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
     int Hkv, int S, float scale, int causal,
     int64_t sqb, int64_t sqs, int64_t sqh,
     int64_t skb, int64_t sks, int64_t skh,
-    int64_t svb, int64_t svs, int64_t svh) {
+    int64_t svb, int64_t svs, int64_t svh,
+    const int* __restrict__ doc) {
   constexpr int DSL = D / 16;
   constexpr int DT32 = D / 32;
   const int n_qt = S / 256;
@@ -596,11 +656,21 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
 
   const int kv_end = causal ? (qt * 256 + 256) : S;
   const int my_kv_end = causal ? (q0w + 32) : S;
-  stage_tile<64, D, 512>(Kb, sks, k_lds[0], threadIdx.x);
-  stage_tile<64, D, 512>(Vb, svs, v_lds[0], threadIdx.x);
-  stage_tile<D, 64, 512>(Ktb, S, kt_lds[0], threadIdx.x);
+  // DOC: as in the v5 forward. The element mask stays inline on every
+  // tile here: hoisting it behind a boundary-tile branch, as the forward
+  // does, pushed this kernel to 256 VGPRs plus scratch.
+  int kv_begin = 0, my_kv_begin = 0, my_ds = 0;
+  if (DOC) {
+    const int* doc_b = doc + (int64_t)b * S;
+    kv_begin = doc_clamp(doc_b[qt * 256], qt * 256) & ~63;
+    my_kv_begin = doc_clamp(doc_b[q0w], q0w) & ~63;
+    my_ds = doc_b[q0w + lo];
+  }
+  stage_tile<64, D, 512>(Kb + (int64_t)kv_begin * sks, sks, k_lds[0], threadIdx.x);
+  stage_tile<64, D, 512>(Vb + (int64_t)kv_begin * svs, svs, v_lds[0], threadIdx.x);
+  stage_tile<D, 64, 512>(Ktb + kv_begin, S, kt_lds[0], threadIdx.x);
   int idx = 0;
-  for (int kv = 0; kv < kv_end; kv += 64, idx ^= 1) {
+  for (int kv = kv_begin; kv < kv_end; kv += 64, idx ^= 1) {
     __syncthreads();
     if (kv + 64 < kv_end) {
       stage_tile<64, D, 512>(Kb + (int64_t)(kv + 64) * sks, sks,
@@ -610,6 +680,7 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
       stage_tile<D, 64, 512>(Ktb + kv + 64, S, kt_lds[idx ^ 1], threadIdx.x);
     }
     if (kv >= my_kv_end) continue;
+    if (DOC && kv < my_kv_begin) continue;
 
     // ---- St = K·Q^T (pre-scaled), dPt = V·dO^T: C[k][q], q = lo
     f32x16 st[2], dpt[2];
@@ -635,6 +706,7 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
         const int kg = kv + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float p = __expf(st[t][r] - lse_q);
         if (causal && kg > q0w + lo) p = 0.f;
+        if (DOC && kg < my_ds) p = 0.f;
         st[t][r] = p * (dpt[t][r] - dl_q) * scale;
       }
     // ---- dS -> A-fragments (same lane-pair exchange as the fwd P)
@@ -683,7 +755,7 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
 // ----------------------------------------------------------- backward dQ
 // Stages K[64][D], V[64][D] (B-operands for S and dP) and Kt[D][64]
 // (B-operand for dQ += dS*K). dO is contiguous [B,S,H,D].
-template <int D>
+template <int D, bool DOC = false>
 __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ Kt,
@@ -692,7 +764,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
     int Hkv, int S, float scale, int causal,
     int64_t sqb, int64_t sqs, int64_t sqh,
     int64_t skb, int64_t sks, int64_t skh,
-    int64_t svb, int64_t svs, int64_t svh) {
+    int64_t svb, int64_t svs, int64_t svh,
+    const int* __restrict__ doc) {
   constexpr int DS = D / 32;
   constexpr int DT = D / 16;
   const int n_qt = S / 64;
@@ -736,12 +809,21 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
   for (int dt = 0; dt < DT; ++dt) dq_acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int kv_end = causal ? (qt * 64 + 64) : S;
-  for (int kv = 0; kv < kv_end; kv += 64) {
+  int kv_begin = 0, my_kv_begin = 0, row_ds[4];  // DOC: as in flash_fwd_kernel
+  if (DOC) {
+    const int* doc_b = doc + (int64_t)b * S;
+    kv_begin = doc_clamp(doc_b[qt * 64], qt * 64) & ~63;
+    my_kv_begin = doc_clamp(doc_b[q0], q0) & ~63;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) row_ds[r] = doc_b[q0 + lg * 4 + r];
+  }
+  for (int kv = kv_begin; kv < kv_end; kv += 64) {
     __syncthreads();
     stage_tile<64, D>(Kb + (int64_t)kv * sks, sks, k_lds, threadIdx.x);
     stage_tile<64, D>(Vb + (int64_t)kv * svs, svs, v_lds, threadIdx.x);
     stage_tile<D, 64>(Ktb + kv, S, kt_lds, threadIdx.x);
     __syncthreads();
+    if (DOC && kv < my_kv_begin) continue;
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
       f32x4 s_acc{0.f, 0.f, 0.f, 0.f}, dp_acc{0.f, 0.f, 0.f, 0.f};
@@ -756,6 +838,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
         const int kg = kv + sub * 16 + li;
         float p = __expf(s_acc[r] * scale - lse_r[r]);
         if (causal && kg > qg) p = 0.f;
+        if (DOC && kg < row_ds[r]) p = 0.f;
         st16_swz<64>(ds_lds, lg * 4 + r, sub * 16 + li,
                      f2bf(p * (dp_acc[r] - dl_r[r]) * scale));
       }
@@ -963,7 +1046,10 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dkv_v5_kernel(
 // barriers, whose zero-gap vmcnt drain shows as this kernel's 9.0
 // wait/busy in the PMC profile). At NW=8 this is exactly the 160 KiB
 // LDS limit: 2x4x16 KiB stages + 8x2x2 KiB P/dS wave buffers.
-template <int D, int NW = 4, int DBUF = 1>  // NW waves x 16 k-rows
+// DOC: doc_end[B][S] bounds the q loop from above — queries at or past
+// the end of the tile's LAST key's document see none of its keys, and
+// monotonicity makes that one lookup exact for the whole tile.
+template <int D, int NW = 4, int DBUF = 1, bool DOC = false>  // NW waves x 16 k-rows
 __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ Qt,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -973,7 +1059,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     int S, float scale, int causal, int splits,
     int64_t sqb, int64_t sqs, int64_t sqh,
     int64_t skb, int64_t sks, int64_t skh,
-    int64_t svb, int64_t svs, int64_t svh) {
+    int64_t svb, int64_t svs, int64_t svh,
+    const int* __restrict__ doc_end) {
   constexpr int DS = D / 32;
   constexpr int DT = D / 16;
   const int n_kt = S / (NW * 16);
@@ -1015,8 +1102,20 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
   }
 
   const int q_start = (causal ? (kt * (NW * 16)) / 64 * 64 : 0) + split * 64;
+  // DOC: q tiles run up to the end of the last key's document, rounded up
+  // to a tile and clamped to S (block-uniform, so n_iter — which drives
+  // the prefetch — is exact for every split and every head of the group);
+  // my_q_end is the same for this wave's last key; key_end[r] masks.
+  int q_end = S, my_q_end = S, key_end[4];
+  if (DOC) {
+    const int* de_b = doc_end + (int64_t)b * S;
+    q_end = (doc_clamp(de_b[kt * (NW * 16) + NW * 16 - 1], S) + 63) & ~63;
+    my_q_end = doc_clamp(de_b[k0 + 15], S);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) key_end[r] = de_b[k0 + lg * 4 + r];
+  }
   const int tiles_per_g =
-      (S > q_start) ? (S - q_start + 64 * splits - 1) / (64 * splits) : 0;
+      (q_end > q_start) ? (q_end - q_start + 64 * splits - 1) / (64 * splits) : 0;
   const int n_iter = group * tiles_per_g;
   const auto stage_it = [&](int it, int buf) {
     const int g_ = it / tiles_per_g;
@@ -1053,6 +1152,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
       // entirely below the diagonal are fully masked — skip their
       // compute (the wave still co-staged and hits the next barrier)
       if (causal && q0g + 64 <= k0) continue;
+      if (DOC && q0g >= my_q_end) continue;  // past this wave's documents
 #pragma unroll
       for (int sub = 0; sub < 4; ++sub) {
         f32x4 st_acc{0.f, 0.f, 0.f, 0.f}, dpt_acc{0.f, 0.f, 0.f, 0.f};
@@ -1071,6 +1171,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
           const int kg = k0 + lg * 4 + r;
           float p = __expf(st_acc[r] * scale - lse_q);
           if (causal && kg > qg) p = 0.f;
+          if (DOC && qg >= key_end[r]) p = 0.f;
           st16_swz<64>(pt_lds, lg * 4 + r, sub * 16 + li, f2bf(p));
           st16_swz<64>(dst_lds, lg * 4 + r, sub * 16 + li,
                        f2bf(p * (dpt_acc[r] - dl_q) * scale));
@@ -1143,10 +1244,29 @@ PRIME_API int prime_flash_fwd(hipStream_t stream, const void* Q, const void* K,
                               int64_t H, int64_t Hkv, int64_t S, int64_t D,
                               double scale, int64_t causal,
                               int64_t sqb, int64_t sqs, int64_t sqh,
-                              int64_t skb, int64_t sks, int64_t skh) {
+                              int64_t skb, int64_t sks, int64_t skh,
+                              const void* doc_start) {
   if (S % 64 != 0 || (D != 64 && D != 128)) return hipErrorInvalidValue;
   static const char* v5env = getenv("PRIME_ATTN_V5");
   static const char* flagenv = getenv("PRIME_ATTN_FLAGS");
+  if (doc_start) {
+    // document-masked instantiations (causal only): the default dispatch
+    // with its default FLAGS; PRIME_ATTN_FLAGS is an A/B knob of the
+    // unmasked kernels and is not honoured here
+    if (!causal) return hipErrorInvalidValue;
+    const bool v5 = (S % 256 == 0) && !(v5env && v5env[0] == '0');
+#define LAUNCH_FWD_DOC(KER, QT, NT)                                          \
+    hipLaunchKernelGGL(KER, dim3((int)(B * H * (S / QT))), dim3(NT), 0,      \
+                       stream, (const bf16*)Q, (const bf16*)K,               \
+                       (const bf16*)Vt, (bf16*)O, (float*)lse, (int)B,       \
+                       (int)H, (int)Hkv, (int)S, (float)scale, 1, sqb, sqs,  \
+                       sqh, skb, sks, skh, (const int*)doc_start)
+    if (v5 && D == 128) LAUNCH_FWD_DOC((flash_fwd_v5_kernel<128, 2, true>), 256, 512);
+    else if (v5) LAUNCH_FWD_DOC((flash_fwd_v5_kernel<64, 2, true>), 256, 512);
+    else if (D == 128) LAUNCH_FWD_DOC((flash_fwd_kernel<128, 4, true>), 64, 256);
+    else LAUNCH_FWD_DOC((flash_fwd_kernel<64, 4, true>), 64, 256);
+    return (int)hipGetLastError();
+  }
   // measured on MI355X (15-iter sweep): FLAGS=2 417 TF > 3 (406) > 0 (387)
   // > 1 (382) — defer-max pays, setprio slightly negative here. The
   // 3-buffer counted-vmcnt variant (FLAGS=6) measured 401-402 vs 417-418
@@ -1165,7 +1285,7 @@ PRIME_API int prime_flash_fwd(hipStream_t stream, const void* Q, const void* K,
                            (const bf16*)K, (const bf16*)Vt, (bf16*)O,
                            (float*)lse, (int)B, (int)H, (int)Hkv, (int)S,
                            (float)scale, (int)causal, sqb, sqs, sqh, skb,
-                           sks, skh);
+                           sks, skh, (const int*)nullptr);
         break;
       default:
         hipLaunchKernelGGL((flash_fwd_v5_kernel<64, 2>), dim3(grid),
@@ -1173,7 +1293,7 @@ PRIME_API int prime_flash_fwd(hipStream_t stream, const void* Q, const void* K,
                            (const bf16*)K, (const bf16*)Vt, (bf16*)O,
                            (float*)lse, (int)B, (int)H, (int)Hkv, (int)S,
                            (float)scale, (int)causal, sqb, sqs, sqh, skb,
-                           sks, skh);
+                           sks, skh, (const int*)nullptr);
         break;
     }
     return (int)hipGetLastError();
@@ -1185,7 +1305,7 @@ PRIME_API int prime_flash_fwd(hipStream_t stream, const void* Q, const void* K,
                        0, stream, (const bf16*)Q, (const bf16*)K,            \
                        (const bf16*)Vt, (bf16*)O, (float*)lse, (int)B,       \
                        (int)H, (int)Hkv, (int)S, (float)scale, (int)causal,  \
-                       sqb, sqs, sqh, skb, sks, skh)
+                       sqb, sqs, sqh, skb, sks, skh, (const int*)nullptr)
     switch (flags & 7) {
       case 0: LAUNCH_V5(0); break;
       case 1: LAUNCH_V5(1); break;
@@ -1202,7 +1322,8 @@ PRIME_API int prime_flash_fwd(hipStream_t stream, const void* Q, const void* K,
                      dim3(NW * 64), 0, stream, (const bf16*)Q,              \
                      (const bf16*)K, (const bf16*)Vt, (bf16*)O, (float*)lse,\
                      (int)B, (int)H, (int)Hkv, (int)S, (float)scale,        \
-                     (int)causal, sqb, sqs, sqh, skb, sks, skh)
+                     (int)causal, sqb, sqs, sqh, skb, sks, skh,              \
+                     (const int*)nullptr)
   // measured: 8-wave 128-row tiles were SLOWER (190 vs 205 TF/s —
   // redundant K/V fetches were already L2-absorbed; wider barriers and
   // +3% causal waste cost more than the halved staging saved)
@@ -1231,11 +1352,29 @@ PRIME_API int prime_flash_bwd_dq(hipStream_t stream, const void* Q,
                                  double scale, int64_t causal,
                                  int64_t sqb, int64_t sqs, int64_t sqh,
                                  int64_t skb, int64_t sks, int64_t skh,
-                                 int64_t svb, int64_t svs, int64_t svh) {
+                                 int64_t svb, int64_t svs, int64_t svh,
+                                 const void* doc_start) {
   if (S % 64 != 0 || (D != 64 && D != 128)) return hipErrorInvalidValue;
   static const char* v5env = getenv("PRIME_ATTN_V5");
   static const char* flagenv = getenv("PRIME_ATTN_FLAGS");
   const int flags = flagenv ? atoi(flagenv) : 2;
+  if (doc_start) {  // document-masked instantiations, default FLAGS
+    if (!causal) return hipErrorInvalidValue;
+    const bool v5 = (S % 256 == 0) && !(v5env && v5env[0] == '0');
+#define LAUNCH_DQ_DOC(KER, QT, NT)                                           \
+    hipLaunchKernelGGL(KER, dim3((int)(B * H * (S / QT))), dim3(NT), 0,      \
+                       stream, (const bf16*)Q, (const bf16*)K,               \
+                       (const bf16*)V, (const bf16*)Kt, (const bf16*)dO,     \
+                       (const float*)lse, (const float*)delta, (bf16*)dQ,    \
+                       (int)B, (int)H, (int)Hkv, (int)S, (float)scale, 1,    \
+                       sqb, sqs, sqh, skb, sks, skh, svb, svs, svh,          \
+                       (const int*)doc_start)
+    if (v5 && D == 128) LAUNCH_DQ_DOC((flash_bwd_dq_v5_kernel<128, 0, true>), 256, 512);
+    else if (v5) LAUNCH_DQ_DOC((flash_bwd_dq_v5_kernel<64, 0, true>), 256, 512);
+    else if (D == 128) LAUNCH_DQ_DOC((flash_bwd_dq_kernel<128, true>), 64, 256);
+    else LAUNCH_DQ_DOC((flash_bwd_dq_kernel<64, true>), 64, 256);
+    return (int)hipGetLastError();
+  }
   if ((D == 64) && (S % 256 == 0) && !(v5env && v5env[0] == '0')) {
     const int grid = (int)(B * H * (S / 256));
     hipLaunchKernelGGL((flash_bwd_dq_v5_kernel<64, 0>), dim3(grid),
@@ -1244,7 +1383,7 @@ PRIME_API int prime_flash_bwd_dq(hipStream_t stream, const void* Q,
                        (const float*)lse, (const float*)delta, (bf16*)dQ,
                        (int)B, (int)H, (int)Hkv, (int)S, (float)scale,
                        (int)causal, sqb, sqs, sqh, skb, sks, skh,
-                       svb, svs, svh);
+                       svb, svs, svh, (const int*)nullptr);
     return (int)hipGetLastError();
   }
   if ((D == 128) && (S % 256 == 0) && !(v5env && v5env[0] == '0')) {
@@ -1256,7 +1395,8 @@ PRIME_API int prime_flash_bwd_dq(hipStream_t stream, const void* Q,
                        (const bf16*)dO, (const float*)lse,                  \
                        (const float*)delta, (bf16*)dQ, (int)B, (int)H,      \
                        (int)Hkv, (int)S, (float)scale, (int)causal,         \
-                       sqb, sqs, sqh, skb, sks, skh, svb, svs, svh)
+                       sqb, sqs, sqh, skb, sks, skh, svb, svs, svh,         \
+                       (const int*)nullptr)
     if (flags & 1) LAUNCH_DQ5(1); else LAUNCH_DQ5(0);
     return (int)hipGetLastError();
   }
@@ -1265,7 +1405,7 @@ PRIME_API int prime_flash_bwd_dq(hipStream_t stream, const void* Q,
              (const bf16*)V, (const bf16*)Kt, (const bf16*)dO,
              (const float*)lse, (const float*)delta, (bf16*)dQ, (int)B, (int)H,
              (int)Hkv, (int)S, (float)scale, (int)causal, sqb, sqs, sqh, skb,
-             sks, skh, svb, svs, svh);
+             sks, skh, svb, svs, svh, (const int*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -1279,8 +1419,10 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
                                   double scale, int64_t causal,
                                   int64_t sqb, int64_t sqs, int64_t sqh,
                                   int64_t skb, int64_t sks, int64_t skh,
-                                  int64_t svb, int64_t svs, int64_t svh) {
+                                  int64_t svb, int64_t svs, int64_t svh,
+                                  const void* doc_end) {
   if (S % 64 != 0 || (D != 64 && D != 128)) return hipErrorInvalidValue;
+  if (doc_end && !causal) return hipErrorInvalidValue;
   // 8-wave blocks: one q/do/qt/dot stage feeds 128 k-rows (half the
   // staging traffic of the 4-wave version); fall back to 4 waves when the
   // sequence doesn't tile by 128
@@ -1292,7 +1434,9 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
   static const char* v5denv = getenv("PRIME_ATTN_DKV5");
   static const char* fenv = getenv("PRIME_ATTN_FLAGS");
   const int flags = fenv ? atoi(fenv) : 2;
-  if ((D == 128) && (S % 256 == 0) && (v5denv && v5denv[0] == '1')) {
+  // the opt-in 32x32 kernel has no document mask: masked calls use the
+  // 16x16 kernel whatever the env var says
+  if (!doc_end && (D == 128) && (S % 256 == 0) && (v5denv && v5denv[0] == '1')) {
     const int sp = (int)(splits > 4 ? 4 : splits);
     const int grid = (int)(B * Hkv * (S / 256) * sp);
 #define LAUNCH_DKV5(F)                                                       \
@@ -1315,8 +1459,10 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
   }
   static const char* nw8env = getenv("PRIME_ATTN_DKV8");
   const bool nw8 = (S % 128 == 0) && !(nw8env && nw8env[0] == '0');
-#define LAUNCH_DKV(DD, NWV, DB)                                              \
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<DD, NWV, DB>),                  \
+#define LAUNCH_DKV(DD, NWV, DB) LAUNCH_DKV_(DD, NWV, DB, false, nullptr)
+#define LAUNCH_DKV_DOC(DD, NWV, DB) LAUNCH_DKV_(DD, NWV, DB, true, doc_end)
+#define LAUNCH_DKV_(DD, NWV, DB, DOCV, DOCP)                                 \
+    hipLaunchKernelGGL((flash_bwd_dkv_kernel<DD, NWV, DB, DOCV>),            \
                        dim3((int)(B * Hkv * (S / (NWV * 16)) * splits)),     \
                        dim3(NWV * 64), 0, stream, (const bf16*)Q,            \
                        (const bf16*)Qt, (const bf16*)K, (const bf16*)V,      \
@@ -1324,10 +1470,18 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
                        (const float*)lse, (const float*)delta, (float*)wsK,  \
                        (float*)wsV, (int)B, (int)H, (int)Hkv, (int)S,        \
                        (float)scale, (int)causal, (int)splits, sqb, sqs,     \
-                       sqh, skb, sks, skh, svb, svs, svh)
+                       sqh, skb, sks, skh, svb, svs, svh, (const int*)DOCP)
   static const char* dbenv = getenv("PRIME_ATTN_DKV_DBUF");
   const bool dbuf = !(dbenv && dbenv[0] == '0');
-  if (nw8 && dbuf) {
+  if (doc_end) {
+    if (nw8 && dbuf) {
+      if (D == 128) LAUNCH_DKV_DOC(128, 8, 2); else LAUNCH_DKV_DOC(64, 8, 2);
+    } else if (nw8) {
+      if (D == 128) LAUNCH_DKV_DOC(128, 8, 1); else LAUNCH_DKV_DOC(64, 8, 1);
+    } else {
+      if (D == 128) LAUNCH_DKV_DOC(128, 4, 1); else LAUNCH_DKV_DOC(64, 4, 1);
+    }
+  } else if (nw8 && dbuf) {
     if (D == 128) LAUNCH_DKV(128, 8, 2); else LAUNCH_DKV(64, 8, 2);
   } else if (nw8) {
     if (D == 128) LAUNCH_DKV(128, 8, 1); else LAUNCH_DKV(64, 8, 1);

@@ -293,6 +293,62 @@ def _check_flash_shape(S: int, D: int) -> None:
         )
 
 
+def doc_starts(tokens: torch.Tensor, eos_id: int) -> torch.Tensor:
+    """tokens [B,S] -> int32 [B,S]: index of the first token of the document
+    each token belongs to. A token that follows an `eos_id` token starts a
+    new document; the EOS itself belongs to the document it ends. Plain
+    torch ops on the tokens' device, no host sync."""
+    B, S = tokens.shape
+    idx = torch.arange(S, device=tokens.device, dtype=torch.int32).expand(B, S)
+    new_doc = torch.zeros(B, S, dtype=torch.bool, device=tokens.device)
+    new_doc[:, 1:] = tokens[:, :-1] == eos_id
+    return torch.where(new_doc, idx, torch.zeros_like(idx)).cummax(dim=1).values
+
+
+def _doc_ends(doc_start: torch.Tensor) -> torch.Tensor:
+    """Mirror of doc_start for the dK/dV kernel: exclusive end of each
+    key's document (the next document's start, or S)."""
+    B, S = doc_start.shape
+    idx = torch.arange(S, device=doc_start.device, dtype=torch.int32).expand(B, S)
+    cand = torch.where(doc_start == idx, idx, torch.full_like(idx, S))
+    # first document start at or after j, then shift by one for "after j"
+    nxt = cand.flip(1).cummin(dim=1).values.flip(1)
+    return torch.cat([nxt[:, 1:], torch.full_like(idx[:, :1], S)], dim=1).contiguous()
+
+
+_DOC_END_CACHE: list = [None, None, None]  # (weakref(doc_start), version, doc_end)
+
+
+def _doc_ends_cached(doc_start: torch.Tensor) -> torch.Tensor:
+    """One doc_start serves every layer of a micro-batch; derive its mirror
+    once, not once per layer's backward."""
+    import weakref
+
+    ref_, ver, val = _DOC_END_CACHE
+    if ref_ is not None and ref_() is doc_start and ver == doc_start._version:
+        return val
+    val = _doc_ends(doc_start)
+    _DOC_END_CACHE[:] = [weakref.ref(doc_start), doc_start._version, val]
+    return val
+
+
+def _check_doc_start(doc_start, q, causal: bool) -> None:
+    B, S = q.shape[0], q.shape[1]
+    if not causal:
+        raise ValueError("flash_attention: doc_start requires causal=True")
+    if not isinstance(doc_start, torch.Tensor) or doc_start.dtype != torch.int32:
+        raise TypeError(
+            "flash_attention: doc_start must be an int32 tensor "
+            f"(got {getattr(doc_start, 'dtype', type(doc_start))})")
+    if tuple(doc_start.shape) != (B, S):
+        raise ValueError(
+            f"flash_attention: doc_start must have shape [B, S] = [{B}, {S}] "
+            f"(got {list(doc_start.shape)})")
+    if doc_start.device != q.device:
+        raise ValueError(
+            f"flash_attention: doc_start is on {doc_start.device}, q on {q.device}")
+
+
 class _FlashAttention(torch.autograd.Function):
     """Stride-aware [B,S,H,D] domain: consumes q/k/v views of the packed
     qkv GEMM output directly (no transposes / .contiguous() on the hot
@@ -300,12 +356,14 @@ class _FlashAttention(torch.autograd.Function):
     for contiguous MFMA B-fragments) are materialized."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float):
+    def forward(ctx, q, k, v, causal: bool, scale: float, doc_start=None):
         B, S, H, D = q.shape
         _check_flash_shape(S, D)
         Hkv = k.shape[2]
         if not (_bshd_ok(q) and _bshd_ok(k) and _bshd_ok(v)):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if doc_start is not None:
+            doc_start = doc_start.contiguous()
         vt = transpose_bshd(v)  # [B,Hkv,D,S]
         o = torch.empty(B, S, H, D, device=q.device, dtype=q.dtype)
         lse = torch.empty(B, S, H, device=q.device, dtype=torch.float32)
@@ -314,18 +372,21 @@ class _FlashAttention(torch.autograd.Function):
                 stream_of(q), ptr(q), ptr(k), ptr(vt), ptr(o), ptr(lse),
                 B, H, Hkv, S, D, scale, int(causal),
                 q.stride(0), q.stride(1), q.stride(2),
-                k.stride(0), k.stride(1), k.stride(2),
+                k.stride(0), k.stride(1), k.stride(2), ptr(doc_start),
             ),
             "flash_fwd",
         )
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.meta = (causal, scale)
+        ctx.doc_start = doc_start  # int mask, no gradient: not a saved tensor
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         causal, scale = ctx.meta
+        doc_start = ctx.doc_start
+        doc_end = _doc_ends_cached(doc_start) if doc_start is not None else None
         B, S, H, D = q.shape
         Hkv = k.shape[2]
         do = do.contiguous()
@@ -343,7 +404,7 @@ class _FlashAttention(torch.autograd.Function):
                 int(causal),
                 q.stride(0), q.stride(1), q.stride(2),
                 k.stride(0), k.stride(1), k.stride(2),
-                v.stride(0), v.stride(1), v.stride(2),
+                v.stride(0), v.stride(1), v.stride(2), ptr(doc_start),
             ),
             "flash_bwd_dq",
         )
@@ -374,18 +435,26 @@ class _FlashAttention(torch.autograd.Function):
                 B, H, Hkv, S, D, scale, int(causal),
                 q.stride(0), q.stride(1), q.stride(2),
                 k.stride(0), k.stride(1), k.stride(2),
-                v.stride(0), v.stride(1), v.stride(2),
+                v.stride(0), v.stride(1), v.stride(2), ptr(doc_end),
             ),
             "flash_bwd_dkv",
         )
-        return dq, dk, dv, None, None
+        return dq, dk, dv, None, None, None
 
 
-def flash_attention(q, k, v, causal: bool = True) -> torch.Tensor:
-    """q: [B,S,H,D]; k,v: [B,S,Hkv,D] (GQA). Returns [B,S,H,D]."""
+def flash_attention(q, k, v, causal: bool = True, doc_start=None) -> torch.Tensor:
+    """q: [B,S,H,D]; k,v: [B,S,Hkv,D] (GQA). Returns [B,S,H,D].
+
+    doc_start: optional int32 [B,S] document mask for packed sequences
+    (see `doc_starts`): query i sees key j iff doc_start[b,i] <= j <= i.
+    One array per micro-batch, shared by all layers and heads."""
+    if doc_start is not None:
+        _check_doc_start(doc_start, q, causal)
     if not _is_hip(q):
-        return ref.attention(q, k, v, causal)
-    return _FlashAttention.apply(q, k, v, causal, q.shape[-1] ** -0.5)
+        return ref.attention(q, k, v, causal, doc_start=doc_start)
+    if doc_start is None:
+        return _FlashAttention.apply(q, k, v, causal, q.shape[-1] ** -0.5)
+    return _FlashAttention.apply(q, k, v, causal, q.shape[-1] ** -0.5, doc_start)
 
 
 # --------------------------------------------------------- cross entropy

@@ -44,10 +44,16 @@ def swiglu(gu: torch.Tensor) -> torch.Tensor:
 
 
 def attention(
-    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True
+    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
+    doc_start: torch.Tensor | None = None,
 ) -> torch.Tensor:
-    """q: [B,S,H,D], k/v: [B,S,Hkv,D] -> [B,S,H,D]. fp32 math."""
+    """q: [B,S,H,D], k/v: [B,S,Hkv,D] -> [B,S,H,D]. fp32 math.
+
+    doc_start: optional int [B,S] document mask (causal only): query i sees
+    key j iff doc_start[b, i] <= j <= i."""
     B, S, H, D = q.shape
+    if doc_start is not None and not causal:
+        raise ValueError("doc_start requires causal=True")
     Hkv = k.shape[2]
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=2)
@@ -59,6 +65,10 @@ def attention(
     if causal:
         mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), 1)
         scores = scores.masked_fill(mask, float("-inf"))
+    if doc_start is not None:
+        j = torch.arange(S, device=q.device).view(1, 1, S)
+        before = j < doc_start.to(q.device).long().view(B, S, 1)  # [B,Sq,Sk]
+        scores = scores.masked_fill(before.unsqueeze(1), float("-inf"))
     p = scores.softmax(-1)
     return (p @ vf).transpose(1, 2).to(q.dtype)
 

@@ -44,6 +44,11 @@ class Trainer:
             raise ValueError("model.fp8 is not supported with parallel.fsdp "
                              "yet (per-step weight caches need stable "
                              "parameter storage)")
+        # a sequence-parallel rank holds a slice of the context and cannot
+        # know where its first document began
+        if cfg.parallel.seq_parallel and cfg.data.doc_mask_eos_id is not None:
+            raise ValueError("data.doc_mask_eos_id is not supported with "
+                             "parallel.seq_parallel")
         self.stop_requested = False
         self.run_dir = Path(run_dir) if run_dir else Path("runs") / cfg.run_name
         self.run_dir.mkdir(parents=True, exist_ok=True)
@@ -248,7 +253,14 @@ class Trainer:
                 r = self.mesh.worker_rank
                 x = x[:, r * sl : (r + 1) * sl]
                 y = y[:, r * sl : (r + 1) * sl]
-            loss = self.model.loss(x, y) / cfg.data.grad_accum
+            if cfg.data.doc_mask_eos_id is None:
+                loss = self.model.loss(x, y)
+            else:  # one mask per micro-batch, shared by every layer
+                from .ops import doc_starts
+
+                loss = self.model.loss(
+                    x, y, doc_start=doc_starts(x, cfg.data.doc_mask_eos_id))
+            loss = loss / cfg.data.grad_accum
             loss.backward()
             loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
         if self.fsdp:

@@ -46,6 +46,10 @@ class DataSection(_Strict):
     # explicit DiLoCo-worker data index; elastic mode derives one from the
     # join sequence when unset so workers never train identical streams
     worker_index: int | None = None
+    # document mask for packed sequences: tokens attend only within their
+    # own document, where a document ends at (and includes) this token id.
+    # None = plain causal attention across the whole window.
+    doc_mask_eos_id: int | None = Field(None, ge=0)
 
 
 class OptimConfig(_Strict):
@@ -152,6 +156,8 @@ activation_checkpointing = false
 kind = "synthetic"          # synthetic | token_file
 micro_batch_size = 4
 grad_accum = 1
+# doc_mask_eos_id = 0       # packed corpus: attend within documents only
+                            # (a document ends at this token id)
 
 [optim]
 lr = 3e-4
