@@ -18,7 +18,7 @@ import sys
 import time
 import uuid
 from pathlib import Path
-from typing import Optional
+from typing import List, Optional
 
 import typer
 from typer.core import TyperGroup
@@ -690,7 +690,9 @@ def eval_cmd(
 @app.command("generate")
 def generate_cmd(
     model: str = typer.Option("llama_150m", help="model preset"),
-    prompt_tokens: str = typer.Option("1,2,3,4", help="comma-separated token ids"),
+    prompt_tokens: List[str] = typer.Option(
+        ["1,2,3,4"], help="comma-separated token ids; repeat the option or "
+        "separate groups with ';' for several prompts (one ragged batch)"),
     prompt: Optional[str] = typer.Option(None, help="text prompt (needs --tokenizer)"),
     tokenizer: Optional[str] = typer.Option(None, help="local tokenizer.json"),
     max_new: int = typer.Option(32),
@@ -734,7 +736,24 @@ def generate_cmd(
 
         ids = encode(tok, prompt)
     else:
-        ids = [int(t) for t in prompt_tokens.split(",")]
+        groups = [g for pt in prompt_tokens for g in pt.split(";") if g.strip()]
+        prompts = [[int(t) for t in g.split(",")] for g in groups]
+        if len(prompts) > 1:
+            # several prompts of different lengths: one ragged batch, one
+            # output line (the new tokens) per prompt
+            from ..models.generate import generate_batch
+
+            outs = generate_batch(m, prompts, max_new, temperature=temperature,
+                                  top_k=top_k, seed=seed)
+            for p_ids, new in zip(prompts, outs):
+                if tok is not None:
+                    from ..utils.tokenizer import decode as tok_decode
+
+                    typer.echo(tok_decode(tok, p_ids + new))
+                else:
+                    typer.echo(",".join(str(t) for t in p_ids + new))
+            return
+        ids = prompts[0]
     toks = torch.tensor([ids], device=dev)
     out = generate(m, toks, max_new, temperature=temperature, top_k=top_k,
                    seed=seed)
@@ -880,6 +899,10 @@ def serve_cmd(
     tokenizer: Optional[str] = typer.Option(None, help="local tokenizer.json"),
     host: str = typer.Option("127.0.0.1"),
     port: int = typer.Option(8392),
+    max_batch: int = typer.Option(8, help="most requests sharing one ragged "
+                                  "decode batch (1 = one request per call)"),
+    batch_window_ms: float = typer.Option(5.0, help="how long the first "
+                                          "waiting request waits for company"),
 ):
     """Serve the model over an OpenAI-style HTTP API (engine-side
     counterpart of the reference's hosted inference surface):
@@ -899,7 +922,9 @@ def serve_cmd(
         secho(str(e), fg="red")
         raise typer.Exit(1)
     secho(f"serving {model} on http://{host}:{port} (ctrl-c to stop)", fg="green")
-    uvicorn.run(create_app(m, model, tok), host=host, port=port,
+    uvicorn.run(create_app(m, model, tok, max_batch=max_batch,
+                           batch_window_ms=batch_window_ms),
+                host=host, port=port,
                 log_level="warning")
 
 

@@ -5,6 +5,10 @@ Prompts are right-padded to a multiple of 64 for the prefill kernel
 (pad keys sit at positions AFTER every real query, so causal masking
 keeps them out of real rows); the caches are then truncated to the true
 prompt length before decoding.
+
+generate() decodes a rectangular batch (one position for all sequences);
+generate_batch() decodes prompts of different lengths together through
+the ragged decode kernels, each sequence at its own position.
 """
 from __future__ import annotations
 
@@ -144,6 +148,207 @@ def _decode_graphed(sess, first_tok, pos0, n_tokens, temperature, top_k, gen):
         out.append(nxt)
         sess["static_tok"].copy_(nxt)
     return out
+
+
+def _per_seq(value, n: int, name: str) -> list:
+    """A scalar option broadcast to n sequences, or one value per sequence."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{name}: got {len(value)} values for {n} prompts")
+        return list(value)
+    return [value] * n
+
+
+def _bucket(n: int) -> int:
+    b = 1
+    while b < n:
+        b *= 2
+    return b
+
+
+@torch.no_grad()
+def generate_batch(
+    model: Llama,
+    prompts,
+    max_new_tokens,
+    temperature=0.0,
+    top_k=0,
+    seed=None,
+    stop_token_ids=None,
+    use_graph: bool = True,
+) -> list[list[int]]:
+    """Ragged batched generation: `prompts` is a list of token-id lists of
+    different lengths; returns the NEW tokens of each. max_new_tokens,
+    temperature, top_k and seed take a scalar or one value per sequence. A
+    sequence ends after its own max_new_tokens or on one of stop_token_ids
+    (the stop token is kept); finished sequences become idle slots of the
+    decode kernels and cause no further KV traffic. Each sequence samples
+    from its own CPU generator, so a seeded request gives the same tokens
+    alone or next to others.
+
+    One batched causal-flash prefill (right-padded; rows past a prompt's
+    length hold junk that is never read: every decode step writes row
+    pos[b] before attending to pos[b] + 1 rows), then one ragged decode pass
+    per token. The batch is padded with idle slots to a power of two; with
+    use_graph on CUDA the per-token pass is a hipGraph captured once per
+    (batch bucket, cache-length bucket, device) that advances its own
+    device-side positions."""
+    model.eval()
+    cfg = model.cfg
+    p0 = next(model.parameters())
+    dev, dtype = p0.device, p0.dtype
+    n = len(prompts)
+    if n == 0:
+        return []
+    prompts = [[int(t) for t in p] for p in prompts]
+    max_new = [int(m) for m in _per_seq(max_new_tokens, n, "max_new_tokens")]
+    temps = _per_seq(temperature, n, "temperature")
+    topks = _per_seq(top_k, n, "top_k")
+    seeds = _per_seq(seed, n, "seed")
+    stops = frozenset(int(t) for t in (stop_token_ids or ()))
+    L0 = [len(p) for p in prompts]
+    for b in range(n):
+        if L0[b] == 0:
+            raise ValueError(f"prompt {b} is empty")
+        if L0[b] + max_new[b] > cfg.max_seq:
+            raise ValueError(f"prompt {b}: {L0[b] + max_new[b]} tokens exceeds "
+                             f"max_seq {cfg.max_seq}")
+    out: list[list[int]] = [[] for _ in range(n)]
+    done = [m <= 0 for m in max_new]
+    if all(done):
+        return out
+    total = max(L0[b] + max(max_new[b], 1) for b in range(n))
+    Bk = _bucket(n)
+    on_gpu = dev.type == "cuda"
+    graphing = use_graph and on_gpu and max(max_new) > 2
+    # cache-length bucket: shared by the graphed and the eager pass, so both
+    # launch the same kernels on the same shapes and agree exactly
+    smax = min(_pad64(cfg.max_seq), _pad64(max(total, 1024))) if on_gpu \
+        else _pad64(total)
+    sessions = getattr(model, "_decode_sessions", None)
+    if sessions is None:
+        sessions = model._decode_sessions = {}
+    key = ("ragged", Bk, smax, dev.index)
+    sess = sessions.get(key) if graphing else None
+    if sess is None:
+        caches = [
+            (
+                torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
+                torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
+            )
+            for _ in range(cfg.n_layers)
+        ]
+        sess = _ragged_state(caches, Bk, dev)
+        if graphing:
+            # capture BEFORE prefill, as _build_session does: the warmup and
+            # capture passes write junk rows that the prefill overwrites
+            _capture_ragged(model, sess)
+            sessions[key] = sess
+    caches = sess["caches"]
+    gens = []
+    for b in range(n):
+        g = torch.Generator(device="cpu")
+        if seeds[b] is not None:
+            g.manual_seed(int(seeds[b]))
+        gens.append(g)
+
+    def pick(logits, rows):
+        """Next token of every sequence in `rows` (logits row = slot)."""
+        greedy = None
+        nxt = {}
+        for b in rows:
+            if temps[b] <= 0:
+                if greedy is None:  # one device sync for all greedy rows
+                    greedy = logits.argmax(-1).tolist()
+                nxt[b] = int(greedy[b])
+            else:
+                nxt[b] = int(_sample(logits[b:b + 1], temps[b], topks[b], gens[b]))
+        return nxt
+
+    def accept(nxt):
+        for b, t in nxt.items():
+            out[b].append(t)
+            if len(out[b]) >= max_new[b] or t in stops:
+                done[b] = True
+
+    # ---- prefill the real sequences (views of the first n cache slots)
+    Lp = _pad64(max(L0))
+    padded = torch.zeros(n, Lp, dtype=torch.int64)
+    for b in range(n):
+        padded[b, :L0[b]] = torch.tensor(prompts[b], dtype=torch.int64)
+    padded = padded.to(dev)
+    pre = [(kc[:n], vc[:n]) for kc, vc in caches]
+    h = model(padded, caches=pre, pos=0)
+    last = torch.tensor([l - 1 for l in L0], device=dev)
+    logits = model.lm_head(h[torch.arange(n, device=dev), last])
+    live = [b for b in range(n) if not done[b]]
+    accept(pick(logits, live))
+
+    # ---- ragged decode: slot b sits at pos[b]; finished / padding = idle
+    def write_state():
+        pos = [-1] * Bk
+        for b in range(n):
+            if not done[b]:
+                pos[b] = L0[b] + len(out[b]) - 1
+        pos_t = torch.tensor(pos, dtype=torch.int32)
+        act_t = (pos_t >= 0).to(torch.int32)
+        sess["pos"].copy_(pos_t)
+        sess["active"].copy_(act_t)
+        sess["lens"].copy_((pos_t + 1) * act_t)
+
+    write_state()
+    tok = torch.zeros(Bk, 1, dtype=torch.int64)
+    while not all(done):
+        live = [b for b in range(n) if not done[b]]
+        for b in live:
+            tok[b, 0] = out[b][-1]
+        sess["tok"].copy_(tok)
+        if graphing:
+            sess["graph"].replay()
+            logits = sess["logits"]
+        else:
+            logits = _ragged_step(model, sess)
+        accept(pick(logits, live))
+        if any(done[b] for b in live):
+            write_state()  # retire finished sequences to idle slots
+    return out
+
+
+def _ragged_state(caches, Bk, dev):
+    """Device-side state of a ragged decode pass (stable pointers for graph
+    replay). Initial values are a safe warm-up state: every slot at row 0."""
+    return {
+        "caches": caches,
+        "tok": torch.zeros(Bk, 1, dtype=torch.int64, device=dev),
+        "pos": torch.zeros(Bk, dtype=torch.int32, device=dev),
+        "lens": torch.ones(Bk, dtype=torch.int32, device=dev),
+        "active": torch.ones(Bk, dtype=torch.int32, device=dev),
+    }
+
+
+def _ragged_step(model, sess):
+    """One token for every live slot, then advance the device-side state:
+    pos += active, lens = (pos + 1) * active (idle slots stay idle)."""
+    h = model(sess["tok"], caches=sess["caches"], seq_pos=sess)
+    logits = model.lm_head(h[:, 0])
+    sess["pos"].add_(sess["active"])
+    torch.mul(sess["pos"] + 1, sess["active"], out=sess["lens"])
+    return logits
+
+
+def _capture_ragged(model, sess):
+    """Capture _ragged_step as one replayable hipGraph (warm-up on a side
+    stream, per the torch CUDA-graphs contract, as _build_session)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            _ragged_step(model, sess)
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        sess["logits"] = _ragged_step(model, sess)
+    sess["graph"] = graph
 
 
 def _sample(logits: torch.Tensor, temperature: float, top_k: int, gen) -> torch.Tensor:

@@ -56,10 +56,27 @@ class Attention(nn.Module):
     sp_group = None
 
     def forward(self, x, cos, sin, cache=None, pos: int = 0, pos_dev=None,
-                doc_start=None):
+                doc_start=None, seq_pos=None):
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
+        if seq_pos is not None:
+            # ragged batched decode: one new token per sequence, each at its
+            # own position (seq_pos["pos"]) and cache length (seq_pos["lens"])
+            if S != 1 or cache is None:
+                raise ValueError("seq_pos (per-sequence decode positions) "
+                                 "needs one token per sequence (S == 1) and "
+                                 "KV caches")
+            if doc_start is not None or pos_dev is not None \
+                    or self.sp_group is not None:
+                raise ValueError("seq_pos cannot be combined with doc_start, "
+                                 "pos_dev or sequence parallelism")
+            kc, vc = cache
+            qkv = self.wqkv(x).view(B, -1)
+            q = ops.decode_qkv_append(qkv, cos, sin, kc, vc, seq_pos["pos"],
+                                      cfg.n_heads, cfg.n_kv_heads)
+            o = ops.attn_decode_ragged(q, kc, vc, seq_pos["lens"])
+            return self.wo(o.reshape(B, 1, cfg.n_heads * hd))
         if doc_start is not None and (cache is not None or pos_dev is not None):
             raise ValueError("doc_start (document mask) is a full-sequence "
                              "training/eval option; the KV-cache and decode "
@@ -143,11 +160,11 @@ class Block(nn.Module):
         self.mlp = MLP(cfg)
 
     def forward(self, x, res, cos, sin, cache=None, pos: int = 0, pos_dev=None,
-                doc_start=None):
+                doc_start=None, seq_pos=None):
         y, s = ops.fused_add_rmsnorm(x, res, self.attn_norm.weight,
                                      self.attn_norm.eps)
         a = self.attn(y, cos, sin, cache=cache, pos=pos, pos_dev=pos_dev,
-                      doc_start=doc_start)
+                      doc_start=doc_start, seq_pos=seq_pos)
         y2, s2 = ops.fused_add_rmsnorm(a, s, self.mlp_norm.weight,
                                        self.mlp_norm.eps)
         return self.mlp(y2), s2
@@ -192,10 +209,14 @@ class Llama(nn.Module):
         self.rope_sin = sin
 
     def forward(self, tokens: torch.Tensor, caches=None, pos: int = 0,
-                pos_dev=None, doc_start=None) -> torch.Tensor:
+                pos_dev=None, doc_start=None, seq_pos=None) -> torch.Tensor:
         """tokens [B,S] -> hidden states [B,S,dim] (pre-lm_head).
         caches: optional per-layer (k,v) KV caches for inference; pos_dev:
         device-scalar position dict for hipGraph-captured decode.
+        seq_pos: ragged batched decode, a dict of int32 [B] device tensors
+        {"pos": position of each sequence's new token (negative = idle slot),
+        "lens": rows it attends to, pos + 1 (0 = idle slot)}; needs S == 1
+        and caches.
         doc_start: optional int32 [B,S] document mask (ops.doc_starts) for
         packed sequences, shared by every layer. Positions are NOT reset per
         document: RoPE is relative, so attention within a document does not
@@ -203,6 +224,14 @@ class Llama(nn.Module):
         if doc_start is not None and (caches or pos_dev is not None):
             raise ValueError("doc_start cannot be combined with KV caches or "
                              "decode positions")
+        if seq_pos is not None:
+            if tokens.shape[1] != 1 or not caches:
+                raise ValueError("seq_pos needs one token per sequence "
+                                 "(S == 1) and KV caches")
+            if doc_start is not None or pos_dev is not None \
+                    or self.sp_pos_offset:
+                raise ValueError("seq_pos cannot be combined with doc_start, "
+                                 "pos_dev or sequence parallelism")
         x = self.tok_embeddings(tokens)
         res = None
         if pos == 0 and self.sp_pos_offset:
@@ -218,7 +247,8 @@ class Llama(nn.Module):
             else:
                 x, res = blk(x, res, cos, sin,
                              cache=caches[i] if caches else None, pos=pos,
-                             pos_dev=pos_dev, doc_start=doc_start)
+                             pos_dev=pos_dev, doc_start=doc_start,
+                             seq_pos=seq_pos)
         y, _ = ops.fused_add_rmsnorm(x, res, self.norm.weight, self.norm.eps)
         return y
 

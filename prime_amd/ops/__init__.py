@@ -19,6 +19,10 @@ from .functional import (
     rope_packed_fwd,
     swiglu_bwd_t,
     attn_decode,
+    attn_decode_ragged,
+    decode_qkv_append,
+    decode_ragged_split,
+    DECODE_RAGGED_CHUNK,
     fused_add_rmsnorm,
     cross_entropy,
     dequant_int8,
@@ -41,6 +45,10 @@ from .build import build, LIB_PATH
 __all__ = [
     "apply_rope",
     "attn_decode",
+    "attn_decode_ragged",
+    "decode_qkv_append",
+    "decode_ragged_split",
+    "DECODE_RAGGED_CHUNK",
     "fused_add_rmsnorm",
     "cross_entropy",
     "dequant_int8",

@@ -79,6 +79,17 @@ __device__ __forceinline__ float block_reduce_max(float x, float* scratch) {
   return r;
 }
 
+// ---- RoPE -----------------------------------------------------------------
+// One rotated pair; every RoPE kernel (rope.hip, decode_prep.hip) goes
+// through it, with `sign` a runtime value, so they all round identically.
+__device__ __forceinline__ void rope_rot(bf16 x1, bf16 x2, float c, float sn,
+                                         float sign, bf16& y1, bf16& y2) {
+  const float a = bf2f(x1), b = bf2f(x2);
+  const float sj = sign * sn;
+  y1 = f2bf(a * c - b * sj);
+  y2 = f2bf(b * c + a * sj);
+}
+
 static inline int prime_grid(int64_t work_items, int block) {
   int64_t g = (work_items + block - 1) / block;
   if (g > PRIME_MAX_GRID) g = PRIME_MAX_GRID;

@@ -8,16 +8,7 @@
 // (backward is rotation by -theta: sign = -1).
 #include "common.h"
 
-// One rotated pair; every RoPE kernel in this file goes through it (with
-// `sign` a runtime value) so they all round identically.
-__device__ __forceinline__ void rope_rot(bf16 x1, bf16 x2, float c, float sn,
-                                         float sign, bf16& y1, bf16& y2) {
-  const float a = bf2f(x1), b = bf2f(x2);
-  const float sj = sign * sn;
-  y1 = f2bf(a * c - b * sj);
-  y2 = f2bf(b * c + a * sj);
-}
-
+// Every kernel here rotates through rope_rot (common.h).
 __global__ void rope_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
                             const float* __restrict__ cos_t,
                             const float* __restrict__ sin_t, int64_t nrows,

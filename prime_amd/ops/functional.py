@@ -1164,6 +1164,131 @@ def attn_decode(q, k_cache, v_cache, length: int, len_dev=None) -> torch.Tensor:
     return o
 
 
+# ------------------------------------------------ ragged (batched) decode
+# Internal boundaries of the ragged decode kernel: the online softmax walks
+# the cache in chunks of DECODE_RAGGED_CHUNK keys, and each (batch, kv head)
+# is split along the sequence into ranges of decode_ragged_split(...) rows.
+DECODE_RAGGED_CHUNK = 256
+_RAGGED_GROUPS = (1, 2, 4, 8)
+_RAGGED_WS: dict = {}  # (B, Hkv, G, D, nsplit, device) -> fp32 partials
+
+
+def decode_ragged_split(B: int, Hkv: int, Smax: int, n_cu: int = 256) -> int:
+    """Rows per sequence split of attn_decode_ragged for a cache shape: a
+    multiple of DECODE_RAGGED_CHUNK aiming at ~4 workgroups per CU. Depends
+    on the launch shape only, never on the lengths, so it is stable under
+    graph replay. The number of splits is ceil(Smax / rows)."""
+    chunks = -(-Smax // DECODE_RAGGED_CHUNK)
+    want = max(1, min(chunks, -(-4 * n_cu // (B * Hkv))))
+    return -(-chunks // want) * DECODE_RAGGED_CHUNK
+
+
+def _n_cu(dev) -> int:
+    return torch.cuda.get_device_properties(dev).multi_processor_count
+
+
+def _check_ragged_shape(H: int, Hkv: int, D: int) -> None:
+    if D not in (64, 128) or H % Hkv != 0 or H // Hkv not in _RAGGED_GROUPS:
+        raise NotImplementedError(
+            f"attn_decode_ragged needs head_dim in {{64, 128}} and a GQA group "
+            f"size in {_RAGGED_GROUPS} (got head_dim={D}, heads={H}, "
+            f"kv_heads={Hkv})")
+
+
+def attn_decode_ragged(q, k_cache, v_cache, lens, split_rows=None) -> torch.Tensor:
+    """Single-token decode with per-sequence lengths: q [B,H,D] (or
+    [B,1,H,D]); sequence b attends to rows [0, lens[b]) of its own caches
+    [B,Smax,Hkv,D]. `lens` is an int32 [B] tensor on q's device, read at
+    kernel time and clamped to [0, Smax]; lens[b] == 0 is an idle slot whose
+    output row is exactly zero and whose cache is not read. `split_rows`
+    overrides decode_ragged_split (a multiple of DECODE_RAGGED_CHUNK)."""
+    if q.dim() == 4:
+        q = q.squeeze(1)
+    B, H, D = q.shape
+    _, Smax, Hkv, _ = k_cache.shape
+    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != q.device:
+        raise ValueError("lens must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        o = torch.zeros_like(q)
+        for b, n in enumerate(lens.tolist()):
+            n = min(max(n, 0), Smax)
+            if n > 0:
+                o[b] = ref.attention(q[b:b + 1].unsqueeze(1), k_cache[b:b + 1, :n],
+                                     v_cache[b:b + 1, :n], causal=False)[0, 0]
+        return o
+    _check_ragged_shape(H, Hkv, D)
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attn_decode_ragged needs contiguous KV caches")
+    if split_rows is None:
+        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % DECODE_RAGGED_CHUNK != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{DECODE_RAGGED_CHUNK} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    G = H // Hkv
+    # one workspace per shape, reused: a captured graph sees stable pointers
+    key = (B, Hkv, G, D, nsplit, q.device.index)
+    ws = _RAGGED_WS.get(key)
+    if ws is None:
+        ws = _RAGGED_WS[key] = torch.empty(
+            B * Hkv, nsplit, G * (D + 2), device=q.device, dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_decode_ragged(
+            stream_of(q), ptr(q), ptr(k_cache), ptr(v_cache), ptr(o), ptr(ws),
+            ptr(lens), B, H, Hkv, Smax, D, split_rows, D**-0.5,
+        ),
+        "attn_decode_ragged",
+    )
+    return o
+
+
+def decode_qkv_append(qkv, cos, sin, k_cache, v_cache, pos, n_heads: int,
+                      n_kv_heads: int) -> torch.Tensor:
+    """Decode-step prep in one launch: qkv [B, (H+2Hkv)*D] is the packed
+    projection of one new token per sequence; rotates q and k at pos[b]
+    (bit-identical to apply_rope(..., pos_offset=pos[b])), writes k and v to
+    row pos[b] of the caches [B,Smax,Hkv,D] and returns the rotated q
+    [B,H,D]. `pos` is an int32 [B] device tensor; a slot with pos[b] < 0 or
+    pos[b] >= min(Smax, len(cos)) is idle: nothing is written for it and its
+    q is zeros."""
+    B = qkv.shape[0]
+    H, Hkv = n_heads, n_kv_heads
+    _, Smax, Hkv_c, D = k_cache.shape
+    T = cos.shape[0]
+    if qkv.dim() != 2 or qkv.shape[1] != (H + 2 * Hkv) * D or Hkv_c != Hkv:
+        raise ValueError(f"decode_qkv_append: qkv {tuple(qkv.shape)} does not "
+                         f"match heads={H}, kv_heads={Hkv}, head_dim={D}")
+    if pos.dtype != torch.int32 or pos.shape != (B,) or pos.device != qkv.device:
+        raise ValueError("pos must be an int32 [B] tensor on qkv's device")
+    if not _is_hip(qkv):
+        q = torch.zeros(B, H, D, dtype=qkv.dtype, device=qkv.device)
+        x = qkv.view(B, 1, H + 2 * Hkv, D)
+        for b, p in enumerate(pos.tolist()):
+            if not 0 <= p < min(Smax, T):
+                continue
+            q[b] = ref.apply_rope(x[b:b + 1, :, :H], cos, sin, p)[0, 0]
+            k_cache[b, p] = ref.apply_rope(x[b:b + 1, :, H:H + Hkv], cos, sin, p)[0, 0]
+            v_cache[b, p] = x[b, 0, H + Hkv:]
+        return q
+    if D not in (64, 128):
+        raise NotImplementedError(
+            f"decode_qkv_append needs head_dim in {{64, 128}} (got {D})")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("decode_qkv_append needs contiguous KV caches")
+    qkv = qkv.contiguous()
+    q = torch.empty(B, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_decode_qkv_append(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(k_cache), ptr(v_cache),
+            ptr(cos), ptr(sin), ptr(pos), B, H, Hkv, D, Smax, T,
+        ),
+        "decode_qkv_append",
+    )
+    return q
+
+
 def mfma_probe32(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     """32x32x16 bf16 MFMA single-tile matmul (layout verification)."""
     C = torch.empty(32, 32, device=A.device, dtype=torch.float32)
