@@ -570,10 +570,14 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
 
 // ------------------------------------------------------- delta = rowsum(dO*O)
 // dO, O: contiguous [B,S,H,D] -> delta [B,S,H] (row-ordered, contiguous)
+// rowc_t (nullable): also writes lse and delta in [B,H,S] order, as
+// rowc_t[0] = lse^T and rowc_t[1] = delta^T, for the dK/dV kernel, whose
+// lanes then read four consecutive queries of one head as one 16-byte load.
 __global__ void attn_delta_kernel(const bf16* __restrict__ dO,
                                   const bf16* __restrict__ O,
                                   float* __restrict__ delta, int64_t rows,
-                                  int D) {
+                                  int D, const float* __restrict__ lse,
+                                  float* __restrict__ rowc_t, int S, int H) {
   const int64_t row0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   for (int64_t r = row0; r < rows; r += (int64_t)gridDim.x * (blockDim.x >> 6)) {
@@ -583,7 +587,18 @@ __global__ void attn_delta_kernel(const bf16* __restrict__ dO,
       acc += bf2f(dO[r * D + i + 1]) * bf2f(O[r * D + i + 1]);
     }
     acc = wave_reduce_sum(acc);
-    if (lane == 0) delta[r] = acc;
+    if (lane == 0) {
+      delta[r] = acc;
+      if (rowc_t) {
+        const int64_t bs = r / H;  // r = (b*S + s)*H + h
+        const int h = (int)(r - bs * H);
+        const int64_t bb = bs / S;
+        const int s = (int)(bs - bb * S);
+        const int64_t t = (bb * H + h) * S + s;
+        rowc_t[t] = lse[r];
+        rowc_t[rows + t] = acc;
+      }
+    }
   }
 }
 
@@ -1039,24 +1054,83 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dkv_v5_kernel(
 }
 
 // -------------------------------------------------------- backward dK, dV
-// Stages Q[64][D], dO[64][D] (B-operands for St and dPt), Qt[D][64] and
-// dOt[D][64] (B-operands for dK and dV accumulation).
+// Stages Q[64][D], dO[64][D] (operands of the score and dP products),
+// Qt[D][64] and dOt[D][64] (operands of the dK and dV accumulation).
+//
+// Tile body (default): St = mfma16(kf, qb) leaves the key on the
+// accumulator row, so each wave passes P and dS through its own LDS
+// buffers (2-byte swizzled stores, a wave-local fence, 16-byte reads) to
+// get them key-on-the-lane for dV += P^T·dO and dK += dS^T·Q. At NW=8,
+// D=128, DBUF=2 that is 2x4x16 KiB stages + 8x2x2 KiB wave buffers =
+// exactly the 160 KiB LDS limit. acc[dt][r] = [k0 + lg*4 + r][dt*16 + li].
+//
+// Tile body, -DPRIME_DKV_KEYLANE=1 (measured SLOWER, kept for A/B: 2.04 vs
+// 1.88 ms whole backward at the bench shape, see profiles): key on the
+// lane. S = mfma16(qb, kf) and dP = mfma16(dob, vf) leave
+// S[q = sub*16 + lg*4 + r][k = k0 + li] in the accumulator — the same
+// registers and LDS reads (the A and B maps mirror each other), roles
+// swapped. For the 32-query half c of the tile a lane's eight values
+// (subs 2c and 2c+1, four rows each), packed to bf16, are then already
+// the B fragment of
+//   dV^T[d][k] += dO^T[d][q] * P[q][k],   dK^T[d][k] += Q^T[d][q] * dS[q][k]
+// with the K dimension in the permuted query order
+//   kidx = lg*8 + j  ->  q = 32c + 16*(j>>2) + lg*4 + (j&3).
+// The A fragment follows the same order: lane (lg, li) reads row
+// d = dt*16 + li of dot_lds/qt_lds as two 8-byte runs at q = 32c + lg*4
+// and q = 32c + 16 + lg*4 (ld4x2_swz). P and dS never touch LDS (128 KiB);
+// acc[dt][r] = [k0 + li][dt*16 + lg*4 + r]. In this body four consecutive
+// queries' lse/delta are one aligned 16-byte load each, issued one q-tile
+// ahead (-DPRIME_DKV_ROWC_PREFETCH=0: at the point of use).
+//
+// lse/delta come from the [B,H,S] copies attn_delta_kernel writes (rowc =
+// {lse_t, delta_t}): the 16 lanes of a group read 16 consecutive floats.
+//
 // DBUF=2: double-buffered q/do/qt/dot stages with prefetch-behind-barrier
-// (one barrier per q-tile instead of the serial stage-between-two-
-// barriers, whose zero-gap vmcnt drain shows as this kernel's 9.0
-// wait/busy in the PMC profile). At NW=8 this is exactly the 160 KiB
-// LDS limit: 2x4x16 KiB stages + 8x2x2 KiB P/dS wave buffers.
+// (one barrier per q-tile).
+// direct=1: the block runs every q-tile of its k-tile and stores bf16
+// dK/dV itself — no reduce kernel, no per-split partials. Causal blocks
+// take k-tile kt and then n_kt-1-kt (their trip counts always add up to
+// the same total), the middle tile of an odd n_kt once. The q-tiles are
+// still taken in `splits` slices, summed in dkv_reduce_kernel's order, so
+// the result has the bits of direct=0: the grid-split q loop with fp32
+// partials in wsK/wsV.
 // DOC: doc_end[B][S] bounds the q loop from above — queries at or past
 // the end of the tile's LAST key's document see none of its keys, and
 // monotonicity makes that one lookup exact for the whole tile.
+__device__ __forceinline__ short8 ld4x2_swz(const bf16* lds_tile, int row,
+                                            int colb) {
+  typedef __attribute__((ext_vector_type(4))) short short4v;
+  const char* base = reinterpret_cast<const char*>(lds_tile) + row * 128;
+  const int sw = (row & 7) << 4;
+  const short4v lo = *reinterpret_cast<const short4v*>(base + (colb ^ sw));
+  const short4v hi = *reinterpret_cast<const short4v*>(base + ((colb + 32) ^ sw));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ short bf_bits(bf16 x) {
+  return (short)__bfloat16_as_ushort(x);
+}
+
+#ifndef PRIME_DKV_KEYLANE
+#define PRIME_DKV_KEYLANE 0  // 1: key-on-the-lane tile body (A/B build)
+#endif
+#ifndef PRIME_DKV_ROWC_PREFETCH
+#define PRIME_DKV_ROWC_PREFETCH 1  // key-on-the-lane body only; 0: load at use
+#endif
+#if !PRIME_DKV_KEYLANE
+#undef PRIME_DKV_ROWC_PREFETCH
+#define PRIME_DKV_ROWC_PREFETCH 0
+#endif
+
 template <int D, int NW = 4, int DBUF = 1, bool DOC = false>  // NW waves x 16 k-rows
 __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ Qt,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
     const bf16* __restrict__ dO, const bf16* __restrict__ dOt,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    float* __restrict__ wsK, float* __restrict__ wsV, int B, int H, int Hkv,
-    int S, float scale, int causal, int splits,
+    const float* __restrict__ rowc,
+    float* __restrict__ wsK, float* __restrict__ wsV,
+    bf16* __restrict__ dK, bf16* __restrict__ dV, int B, int H, int Hkv,
+    int S, float scale, int causal, int splits, int direct,
     int64_t sqb, int64_t sqs, int64_t sqh,
     int64_t skb, int64_t sks, int64_t skh,
     int64_t svb, int64_t svs, int64_t svh,
@@ -1064,29 +1138,54 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
   constexpr int DS = D / 32;
   constexpr int DT = D / 16;
   const int n_kt = S / (NW * 16);
-  const int per_split = (B * Hkv) * n_kt;
-  const int split = blockIdx.x / per_split;
-  const int rem = blockIdx.x - split * per_split;
-  const int bh = rem / n_kt;
-  const int kt = rem - bh * n_kt;
+  // direct + causal: one block per pair (kt, n_kt-1-kt); otherwise one
+  // block per (split, k-tile)
+  const bool paired = direct && causal;
+  const int per_bh = paired ? (n_kt + 1) / 2 : n_kt;
+  const int per_split = (B * Hkv) * per_bh;
+  const int blk_split = blockIdx.x / per_split;  // 0 when direct
+  const int rem = blockIdx.x - blk_split * per_split;
+  const int bh = rem / per_bh;
+  const int kt0 = rem - bh * per_bh;
+  const int n_pass = (paired && kt0 != n_kt - 1 - kt0) ? 2 : 1;
   const int b = bh / Hkv, hkv = bh - b * Hkv;
   const int group = H / Hkv;
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int lg = lane >> 4, li = lane & 15;
-  const int k0 = kt * (NW * 16) + wid * 16;
 
   const bf16* Kb = K + b * skb + hkv * skh;
   const bf16* Vb = V + b * svb + hkv * svh;
+  const float* lse_t = rowc + (int64_t)b * H * S;
+  const float* dl_t = lse_t + (int64_t)B * H * S;
 
   __shared__ bf16 q_lds[DBUF][64 * D];
   __shared__ bf16 do_lds[DBUF][64 * D];
   __shared__ bf16 qt_lds[DBUF][D * 64];
   __shared__ bf16 dot_lds[DBUF][D * 64];
+#if !PRIME_DKV_KEYLANE
   __shared__ bf16 pt_lds_all[NW][16 * 64];
   __shared__ bf16 dst_lds_all[NW][16 * 64];
   bf16* pt_lds = pt_lds_all[wid];
   bf16* dst_lds = dst_lds_all[wid];
+#endif
+
+  // direct: the block walks the `splits` q-loop slices of its k-tile one
+  // after the other, each from zeroed accumulators and in the order a
+  // split-mode block takes them, and adds the slices up in the order
+  // dkv_reduce_kernel does — so both modes give the same bits. The running
+  // sum of slices 0..vs-1 waits in ws[0] (each thread re-reads only what
+  // it wrote itself).
+  const int n_vs = direct ? splits : 1;
+  for (int pv = 0; pv < n_pass * n_vs; ++pv) {
+  const int pass = pv / n_vs;
+  const int vs = pv - pass * n_vs;
+  const int split = direct ? vs : blk_split;
+  const int kt = pass ? n_kt - 1 - kt0 : kt0;
+  const int k0 = kt * (NW * 16) + wid * 16;
+  // every wave must be done reading the stage images of the previous
+  // slice or k-tile before they are primed again
+  if (pv) __syncthreads();
 
   short8 kf[DS], vf[DS];
 #pragma unroll
@@ -1105,15 +1204,22 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
   // DOC: q tiles run up to the end of the last key's document, rounded up
   // to a tile and clamped to S (block-uniform, so n_iter — which drives
   // the prefetch — is exact for every split and every head of the group);
-  // my_q_end is the same for this wave's last key; key_end[r] masks.
-  int q_end = S, my_q_end = S, key_end[4];
+  // my_q_end is the same for this wave's last key; key_end masks this
+  // lane's key.
+  int q_end = S, my_q_end = S, key_end = S;
   if (DOC) {
     const int* de_b = doc_end + (int64_t)b * S;
     q_end = (doc_clamp(de_b[kt * (NW * 16) + NW * 16 - 1], S) + 63) & ~63;
     my_q_end = doc_clamp(de_b[k0 + 15], S);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) key_end[r] = de_b[k0 + lg * 4 + r];
+    key_end = de_b[k0 + li];
   }
+#if !PRIME_DKV_KEYLANE
+  int key_end4[4] = {S, S, S, S};
+  if (DOC) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) key_end4[r] = doc_end[(int64_t)b * S + k0 + lg * 4 + r];
+  }
+#endif
   const int tiles_per_g =
       (q_end > q_start) ? (q_end - q_start + 64 * splits - 1) / (64 * splits) : 0;
   const int n_iter = group * tiles_per_g;
@@ -1130,14 +1236,30 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     stage_tile<D, 64, NW * 64>(Qtb_ + q0g_, S, qt_lds[buf], threadIdx.x);
     stage_tile<D, 64, NW * 64>(dOtb_ + q0g_, S, dot_lds[buf], threadIdx.x);
   };
+  // row constants of q-tile `it`, sub-tile `sub`: queries q0g + sub*16 +
+  // lg*4 .. +3 of head h (it < n_iter: always inside [0, S))
+  const auto rowc_off = [&](int it, int sub) {
+    const int g_ = it / tiles_per_g;
+    const int q0g_ = q_start + (it - g_ * tiles_per_g) * 64 * splits;
+    return (int64_t)(hkv * group + g_) * S + q0g_ + sub * 16 + lg * 4;
+  };
+  f32x4 lse_r[4], dl_r[4];
+  if (PRIME_DKV_ROWC_PREFETCH && n_iter > 0) {
+#pragma unroll
+    for (int sub = 0; sub < 4; ++sub) {
+      const int64_t o = rowc_off(0, sub);
+      lse_r[sub] = *reinterpret_cast<const f32x4*>(lse_t + o);
+      dl_r[sub] = *reinterpret_cast<const f32x4*>(dl_t + o);
+    }
+  }
   if (DBUF == 2 && n_iter > 0) stage_it(0, 0);
   for (int it = 0; it < n_iter; ++it) {
     const int g = it / tiles_per_g;
     const int q0g = q_start + (it - g * tiles_per_g) * 64 * splits;
-    const int h = hkv * group + g;
-    const float* lse_b = lse + (int64_t)b * S * H + h;
-    const float* dl_b = delta + (int64_t)b * S * H + h;
     const int cur = (DBUF == 2) ? (it & 1) : 0;
+    // the tile whose row constants are fetched during this one (the last
+    // iteration re-reads its own: in range, never used)
+    const int itn = (it + 1 < n_iter) ? it + 1 : it;
     {
       __syncthreads();
       if (DBUF == 2) {
@@ -1151,8 +1273,19 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
       // per-wave causal clip: this wave's k-rows start at k0, so q-tiles
       // entirely below the diagonal are fully masked — skip their
       // compute (the wave still co-staged and hits the next barrier)
-      if (causal && q0g + 64 <= k0) continue;
-      if (DOC && q0g >= my_q_end) continue;  // past this wave's documents
+      const bool skip = (causal && q0g + 64 <= k0) || (DOC && q0g >= my_q_end);
+      if (skip) {
+        if (PRIME_DKV_ROWC_PREFETCH) {
+#pragma unroll
+          for (int sub = 0; sub < 4; ++sub) {
+            const int64_t o = rowc_off(itn, sub);
+            lse_r[sub] = *reinterpret_cast<const f32x4*>(lse_t + o);
+            dl_r[sub] = *reinterpret_cast<const f32x4*>(dl_t + o);
+          }
+        }
+        continue;
+      }
+#if !PRIME_DKV_KEYLANE
 #pragma unroll
       for (int sub = 0; sub < 4; ++sub) {
         f32x4 st_acc{0.f, 0.f, 0.f, 0.f}, dpt_acc{0.f, 0.f, 0.f, 0.f};
@@ -1164,14 +1297,14 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
           dpt_acc = mfma16(vf[ds], dob, dpt_acc);
         }
         const int qg = q0g + sub * 16 + li;
-        const float lse_q = lse_b[(int64_t)qg * H];
-        const float dl_q = dl_b[(int64_t)qg * H];
+        const int64_t o = (int64_t)(hkv * group + g) * S + qg;
+        const float lse_q = lse_t[o];
+        const float dl_q = dl_t[o];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int kg = k0 + lg * 4 + r;
           float p = __expf(st_acc[r] * scale - lse_q);
-          if (causal && kg > qg) p = 0.f;
-          if (DOC && qg >= key_end[r]) p = 0.f;
+          if (causal && k0 + lg * 4 + r > qg) p = 0.f;
+          if (DOC && qg >= key_end4[r]) p = 0.f;
           st16_swz<64>(pt_lds, lg * 4 + r, sub * 16 + li, f2bf(p));
           st16_swz<64>(dst_lds, lg * 4 + r, sub * 16 + li,
                        f2bf(p * (dpt_acc[r] - dl_q) * scale));
@@ -1187,19 +1320,120 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
           dv_acc[dt] = mfma16(pa, ld8_swz<64>(dot_lds[cur], dt * 16 + li, ks * 64 + lg * 16), dv_acc[dt]);
           dk_acc[dt] = mfma16(da, ld8_swz<64>(qt_lds[cur], dt * 16 + li, ks * 64 + lg * 16), dk_acc[dt]);
         }
+#else
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        short8 pb, dsb;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const int sub = c * 2 + s2;
+          f32x4 s_acc{0.f, 0.f, 0.f, 0.f}, dp_acc{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ds = 0; ds < DS; ++ds) {
+            const short8 qb = ld8_swz<D>(q_lds[cur], sub * 16 + li, ds * 64 + lg * 16);
+            const short8 dob = ld8_swz<D>(do_lds[cur], sub * 16 + li, ds * 64 + lg * 16);
+            s_acc = mfma16(qb, kf[ds], s_acc);
+            dp_acc = mfma16(dob, vf[ds], dp_acc);
+          }
+          f32x4 lse_q, dl_q;
+          if (PRIME_DKV_ROWC_PREFETCH) {
+            lse_q = lse_r[sub];
+            dl_q = dl_r[sub];
+            const int64_t o = rowc_off(itn, sub);
+            lse_r[sub] = *reinterpret_cast<const f32x4*>(lse_t + o);
+            dl_r[sub] = *reinterpret_cast<const f32x4*>(dl_t + o);
+          } else {
+            const int64_t o = rowc_off(it, sub);
+            lse_q = *reinterpret_cast<const f32x4*>(lse_t + o);
+            dl_q = *reinterpret_cast<const f32x4*>(dl_t + o);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int qg = q0g + sub * 16 + lg * 4 + r;
+            float p = __expf(s_acc[r] * scale - lse_q[r]);
+            if (causal && k0 + li > qg) p = 0.f;
+            if (DOC && qg >= key_end) p = 0.f;
+            pb[s2 * 4 + r] = bf_bits(f2bf(p));
+            dsb[s2 * 4 + r] = bf_bits(f2bf(p * (dp_acc[r] - dl_q[r]) * scale));
+          }
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          const short8 dota = ld4x2_swz(dot_lds[cur], dt * 16 + li, c * 64 + lg * 8);
+          const short8 qta = ld4x2_swz(qt_lds[cur], dt * 16 + li, c * 64 + lg * 8);
+          dv_acc[dt] = mfma16(dota, pb, dv_acc[dt]);
+          dk_acc[dt] = mfma16(qta, dsb, dk_acc[dt]);
+        }
+      }
+#endif
     }
   }
-  // fp32 partials: ws[split][b][hkv][kg][d]
+#if !PRIME_DKV_KEYLANE
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int kg = k0 + lg * 4 + r;
-    const int64_t base = ((((int64_t)split * B + b) * Hkv + hkv) * S + kg) * D;
+  for (int r = 0; r < 4; ++r) {  // acc[dt][r] = [k0 + lg*4 + r][dt*16 + li]
+    const int kr = k0 + lg * 4 + r;
+    const int64_t ob = (((int64_t)b * S + kr) * Hkv + hkv) * D + li;
+    const int64_t wb = ((((int64_t)blk_split * B + b) * Hkv + hkv) * S + kr) * D + li;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
-      wsK[base + dt * 16 + li] = dk_acc[dt][r];
-      wsV[base + dt * 16 + li] = dv_acc[dt][r];
+      if (direct) {
+        // sum = ((0 + slice0) + slice1) + ..., as dkv_reduce_kernel adds
+        float sk = 0.f + dk_acc[dt][r], sv = 0.f + dv_acc[dt][r];
+        if (vs > 0) {
+          sk = wsK[wb + dt * 16] + dk_acc[dt][r];
+          sv = wsV[wb + dt * 16] + dv_acc[dt][r];
+        }
+        if (vs + 1 < n_vs) {
+          wsK[wb + dt * 16] = sk;
+          wsV[wb + dt * 16] = sv;
+        } else {
+          dK[ob + dt * 16] = f2bf(sk);
+          dV[ob + dt * 16] = f2bf(sv);
+        }
+      } else {
+        wsK[wb + dt * 16] = dk_acc[dt][r];
+        wsV[wb + dt * 16] = dv_acc[dt][r];
+      }
     }
   }
+#else
+  const int kg = k0 + li;
+  const int64_t wbase = ((((int64_t)blk_split * B + b) * Hkv + hkv) * S + kg) * D + lg * 4;
+  if (direct) {
+    // bf16 dK/dV [B,S,Hkv,D]: four consecutive d per lane, 8-byte stores
+    const int64_t base = (((int64_t)b * S + kg) * Hkv + hkv) * D + lg * 4;
+    const f32x4 zero{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      f32x4 sk = zero + dk_acc[dt], sv = zero + dv_acc[dt];
+      if (vs > 0) {
+        sk = *reinterpret_cast<f32x4*>(wsK + wbase + dt * 16) + dk_acc[dt];
+        sv = *reinterpret_cast<f32x4*>(wsV + wbase + dt * 16) + dv_acc[dt];
+      }
+      if (vs + 1 < n_vs) {
+        *reinterpret_cast<f32x4*>(wsK + wbase + dt * 16) = sk;
+        *reinterpret_cast<f32x4*>(wsV + wbase + dt * 16) = sv;
+      } else {
+        bf16x4 ok, ov;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          ok.v[r] = f2bf(sk[r]);
+          ov.v[r] = f2bf(sv[r]);
+        }
+        *reinterpret_cast<bf16x4*>(dK + base + dt * 16) = ok;
+        *reinterpret_cast<bf16x4*>(dV + base + dt * 16) = ov;
+      }
+    }
+  } else {
+    // fp32 partials: ws[split][b][hkv][kg][d]
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      *reinterpret_cast<f32x4*>(wsK + wbase + dt * 16) = dk_acc[dt];
+      *reinterpret_cast<f32x4*>(wsV + wbase + dt * 16) = dv_acc[dt];
+    }
+  }
+#endif
+  }  // k-tile pass x q-loop slice
 }
 
 // reduce fp32 split-partials -> bf16 dK/dV in [B,S,Hkv,D]
@@ -1340,7 +1574,21 @@ PRIME_API int prime_attn_delta(hipStream_t stream, const void* dO,
   int grid = prime_grid(rows * 64, 256);
   hipLaunchKernelGGL(attn_delta_kernel, dim3(grid), dim3(256), 0, stream,
                      (const bf16*)dO, (const bf16*)O, (float*)delta, rows,
-                     (int)D);
+                     (int)D, (const float*)nullptr, (float*)nullptr, 1, 1);
+  return (int)hipGetLastError();
+}
+
+// delta [B,S,H] as above, plus rowc_t [2][B][H][S] = {lse^T, delta^T}
+PRIME_API int prime_attn_delta_t(hipStream_t stream, const void* dO,
+                                 const void* O, const void* lse, void* delta,
+                                 void* rowc_t, int64_t B, int64_t S, int64_t H,
+                                 int64_t D) {
+  if (!lse || !rowc_t) return hipErrorInvalidValue;
+  const int64_t rows = B * S * H;
+  int grid = prime_grid(rows * 64, 256);
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(grid), dim3(256), 0, stream,
+                     (const bf16*)dO, (const bf16*)O, (float*)delta, rows,
+                     (int)D, (const float*)lse, (float*)rowc_t, (int)S, (int)H);
   return (int)hipGetLastError();
 }
 
@@ -1409,10 +1657,51 @@ PRIME_API int prime_flash_bwd_dq(hipStream_t stream, const void* Q,
   return (int)hipGetLastError();
 }
 
+static bool dkv_v5_selected(bool doc, int64_t D, int64_t S) {
+  static const char* v5denv = getenv("PRIME_ATTN_DKV5");
+  return !doc && (D == 128) && (S % 256 == 0) && (v5denv && v5denv[0] == '1');
+}
+
+static bool dkv_nw8(int64_t S) {
+  static const char* nw8env = getenv("PRIME_ATTN_DKV8");
+  return (S % 128 == 0) && !(nw8env && nw8env[0] == '0');
+}
+
+// dK/dV mode selection, the one place it is decided: 1 = direct output
+// (one block per k-tile, or per causal pair of k-tiles; bf16 dK/dV stored
+// by the kernel, no workspace), 0 = grid-split q loop with fp32 partials
+// and dkv_reduce_kernel. A block's stage images take more than half the
+// LDS, so one block runs per CU: direct mode is used when its grid has at
+// least one block for every CU, and the split path — which exists to
+// make more, shorter blocks — otherwise (e.g. B=1). The callers size
+// their workspace by this answer. PRIME_ATTN_DKV_DIRECT=1 / =0 forces
+// either mode (read on every call, so one process can A/B them).
+PRIME_API int prime_flash_bwd_dkv_direct(int64_t B, int64_t Hkv, int64_t S,
+                                         int64_t D, int64_t causal,
+                                         int64_t has_doc) {
+  if (dkv_v5_selected(has_doc != 0, D, S)) return 0;  // opt-in kernel: split only
+  const char* env = getenv("PRIME_ATTN_DKV_DIRECT");
+  if (env && env[0] == '1') return 1;
+  if (env && env[0] == '0') return 0;
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+    n_cu = n;
+  }
+  const int64_t n_kt = S / (dkv_nw8(S) ? 128 : 64);
+  const int64_t blocks = B * Hkv * (causal ? (n_kt + 1) / 2 : n_kt);
+  return blocks >= n_cu ? 1 : 0;
+}
+
 PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
                                   const void* Qt, const void* K, const void* V,
                                   const void* dO, const void* dOt,
-                                  const void* lse, const void* delta, void* dK,
+                                  const void* lse, const void* delta,
+                                  const void* rowc, void* dK,
                                   void* dV, void* wsK, void* wsV,
                                   int64_t splits, int64_t B, int64_t H,
                                   int64_t Hkv, int64_t S, int64_t D,
@@ -1431,12 +1720,17 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
   // register budget, and demoting them to inline L2 loads puts ~16 global
   // loads in every q-step's MFMA dependency chain). Opt-in for further
   // work via PRIME_ATTN_DKV5=1; see profiles/10b_1gpu_profile.md.
-  static const char* v5denv = getenv("PRIME_ATTN_DKV5");
   static const char* fenv = getenv("PRIME_ATTN_FLAGS");
   const int flags = fenv ? atoi(fenv) : 2;
+  const bool direct =
+      prime_flash_bwd_dkv_direct(B, Hkv, S, D, causal, doc_end != nullptr) != 0;
+  if (splits < 1) return hipErrorInvalidValue;
+  // direct mode parks its running sum in one slice of workspace when the
+  // q loop is walked in more than one slice
+  if ((!direct || splits > 1) && (!wsK || !wsV)) return hipErrorInvalidValue;
   // the opt-in 32x32 kernel has no document mask: masked calls use the
   // 16x16 kernel whatever the env var says
-  if (!doc_end && (D == 128) && (S % 256 == 0) && (v5denv && v5denv[0] == '1')) {
+  if (dkv_v5_selected(doc_end != nullptr, D, S)) {
     const int sp = (int)(splits > 4 ? 4 : splits);
     const int grid = (int)(B * Hkv * (S / 256) * sp);
 #define LAUNCH_DKV5(F)                                                       \
@@ -1457,20 +1751,24 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
                        (bf16*)dV, (int)B, (int)Hkv, (int)S, (int)D, sp);
     return (int)hipGetLastError();
   }
-  static const char* nw8env = getenv("PRIME_ATTN_DKV8");
-  const bool nw8 = (S % 128 == 0) && !(nw8env && nw8env[0] == '0');
+  if (!rowc) return hipErrorInvalidValue;
+  const bool nw8 = dkv_nw8(S);
+  // blocks per (b, kv head): k-tiles, or causal pairs of them when direct
+  const int64_t n_kt = S / (nw8 ? 128 : 64);
+  const int64_t per_bh = (direct && causal) ? (n_kt + 1) / 2 : n_kt;
 #define LAUNCH_DKV(DD, NWV, DB) LAUNCH_DKV_(DD, NWV, DB, false, nullptr)
 #define LAUNCH_DKV_DOC(DD, NWV, DB) LAUNCH_DKV_(DD, NWV, DB, true, doc_end)
 #define LAUNCH_DKV_(DD, NWV, DB, DOCV, DOCP)                                 \
     hipLaunchKernelGGL((flash_bwd_dkv_kernel<DD, NWV, DB, DOCV>),            \
-                       dim3((int)(B * Hkv * (S / (NWV * 16)) * splits)),     \
+                       dim3((int)(B * Hkv * per_bh * (direct ? 1 : splits))), \
                        dim3(NWV * 64), 0, stream, (const bf16*)Q,            \
                        (const bf16*)Qt, (const bf16*)K, (const bf16*)V,      \
                        (const bf16*)dO, (const bf16*)dOt,                    \
-                       (const float*)lse, (const float*)delta, (float*)wsK,  \
-                       (float*)wsV, (int)B, (int)H, (int)Hkv, (int)S,        \
-                       (float)scale, (int)causal, (int)splits, sqb, sqs,     \
-                       sqh, skb, sks, skh, svb, svs, svh, (const int*)DOCP)
+                       (const float*)rowc, (float*)wsK, (float*)wsV,         \
+                       (bf16*)dK, (bf16*)dV, (int)B, (int)H, (int)Hkv,       \
+                       (int)S, (float)scale, (int)causal, (int)splits,       \
+                       (int)direct, sqb, sqs, sqh, skb, sks, skh, svb, svs,  \
+                       svh, (const int*)DOCP)
   static const char* dbenv = getenv("PRIME_ATTN_DKV_DBUF");
   const bool dbuf = !(dbenv && dbenv[0] == '0');
   if (doc_end) {
@@ -1489,7 +1787,7 @@ PRIME_API int prime_flash_bwd_dkv(hipStream_t stream, const void* Q,
     if (D == 128) LAUNCH_DKV(128, 4, 1); else LAUNCH_DKV(64, 4, 1);
   }
   int err = hipGetLastError();
-  if (err) return err;
+  if (err || direct) return err;
   int rgrid = prime_grid(B * Hkv * S * D, 256);
   hipLaunchKernelGGL(dkv_reduce_kernel, dim3(rgrid), dim3(256), 0, stream,
                      (const float*)wsK, (const float*)wsV, (bf16*)dK,

@@ -391,8 +391,11 @@ class _FlashAttention(torch.autograd.Function):
         Hkv = k.shape[2]
         do = do.contiguous()
         delta = torch.empty(B * S * H, device=q.device, dtype=torch.float32)
+        # rowc = {lse, delta} again in [B,H,S] order, for the dK/dV kernel
+        rowc = torch.empty(2, B, H, S, device=q.device, dtype=torch.float32)
         check(
-            lib().prime_attn_delta(stream_of(q), ptr(do), ptr(o), ptr(delta), B * S * H, D),
+            lib().prime_attn_delta_t(stream_of(q), ptr(do), ptr(o), ptr(lse), ptr(delta),
+                                     ptr(rowc), B, S, H, D),
             "attn_delta",
         )
         kt = transpose_bshd(k)  # [B,Hkv,D,S]
@@ -412,10 +415,15 @@ class _FlashAttention(torch.autograd.Function):
         dot = transpose_bshd(do)
         dk = torch.empty(B, S, Hkv, D, device=q.device, dtype=q.dtype)
         dv = torch.empty(B, S, Hkv, D, device=q.device, dtype=q.dtype)
-        # split the causal q loop across the grid: the unsplit grid is only
-        # B*Hkv*S/64 blocks with 1..S/64 trip-count imbalance
+        # the library picks the mode (see prime_flash_bwd_dkv_direct). Split:
+        # the q loop is cut into `splits` slices spread across the grid, one
+        # fp32 partial each. Direct: one block walks the same slices itself
+        # and adds them up in the same order (same bits), parking the
+        # running sum in a single slice of workspace — none for one slice.
         import os
 
+        direct = bool(lib().prime_flash_bwd_dkv_direct(
+            B, Hkv, S, D, int(causal), int(doc_end is not None)))
         env = os.environ.get("PRIME_AMD_DKV_SPLITS")
         if env:
             splits = max(1, min(int(env), S // 64))
@@ -425,13 +433,14 @@ class _FlashAttention(torch.autograd.Function):
             # wants 8 (12,690 vs 12,593 tok/s — causal trip imbalance
             # dominates at long context)
             splits = max(1, min(8, S // 1024, S // 64))
-        ws = torch.empty(2, splits, B, Hkv, S, D, device=q.device,
-                         dtype=torch.float32)
+        ws_slices = (0 if splits == 1 else 1) if direct else splits
+        ws = torch.empty(2, ws_slices, B, Hkv, S, D, device=q.device,
+                         dtype=torch.float32) if ws_slices else None
         check(
             lib().prime_flash_bwd_dkv(
                 stream_of(q), ptr(q), ptr(qt), ptr(k), ptr(v), ptr(do),
-                ptr(dot), ptr(lse), ptr(delta), ptr(dk), ptr(dv),
-                ptr(ws[0]), ptr(ws[1]), splits,
+                ptr(dot), ptr(lse), ptr(delta), ptr(rowc), ptr(dk), ptr(dv),
+                ptr(None if ws is None else ws[0]), ptr(None if ws is None else ws[1]), splits,
                 B, H, Hkv, S, D, scale, int(causal),
                 q.stride(0), q.stride(1), q.stride(2),
                 k.stride(0), k.stride(1), k.stride(2),
