@@ -129,7 +129,9 @@ PRIME_API int prime_rowwise_quant_fp8(hipStream_t stream, const void* x,
                                       void* y, void* sinv_out, int64_t R,
                                       int64_t C, int64_t e5m2) {
   if (C % 8) return hipErrorInvalidValue;
-  const int grid = (int)(R < 2048 ? R : 2048);
+  // no rows: one idle block, as every other op here (a grid of 0 is a
+  // launch error)
+  const int grid = prime_grid(R, 1);
   if (e5m2)
     hipLaunchKernelGGL((rowwise_quant_fp8_kernel<1>), dim3(grid), dim3(256),
                        0, stream, (const bf16*)x, (unsigned char*)y,

@@ -54,6 +54,7 @@ PRIME_API int prime_transpose_bshd(hipStream_t stream, const void* src,
   if (S % 64 != 0 || D % 64 != 0) return hipErrorInvalidValue;
   const int64_t grid = B * H * (S / 64) * (D / 64);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if (grid == 0) return (int)hipSuccess;  // empty input: nothing to move
   hipLaunchKernelGGL(transpose_bshd_kernel, dim3((int)grid), dim3(256), 0,
                      stream, (const bf16*)src, (bf16*)dst, (int)B, (int)S,
                      (int)H, (int)D, sb, ss, sh);
@@ -135,6 +136,7 @@ PRIME_API int prime_transpose_fp8(hipStream_t stream, const void* src,
   if (S % 64 != 0 || D % 64 != 0) return hipErrorInvalidValue;
   const int64_t grid = B * H * (S / 64) * (D / 64);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if (grid == 0) return (int)hipSuccess;  // empty input: nothing to move
   if (e5m2)
     hipLaunchKernelGGL((transpose_fp8_kernel<1>), dim3((int)grid), dim3(256),
                        0, stream, (const bf16*)src, (unsigned char*)dst,
