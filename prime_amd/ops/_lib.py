@@ -38,10 +38,9 @@ _SIGS = {
     "prime_nesterov_outer": [ctypes.c_void_p] * 6 + [ctypes.c_int64] + [ctypes.c_double] * 2,
     "prime_cross_entropy": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 2 + [ctypes.c_double] + [ctypes.c_int64] * 2,
     "prime_flash_fwd": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 5 + [ctypes.c_double] + [ctypes.c_int64] * 7 + [ctypes.c_void_p],
-    "prime_attn_delta": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 2,
     "prime_flash_bwd_dq": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 5 + [ctypes.c_double] + [ctypes.c_int64] * 10 + [ctypes.c_void_p],
     "prime_attn_delta_t": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 4,
-    "prime_flash_bwd_dkv": [ctypes.c_void_p] * 14 + [ctypes.c_int64] * 6 + [ctypes.c_double] + [ctypes.c_int64] * 10 + [ctypes.c_void_p],
+    "prime_flash_bwd_dkv": [ctypes.c_void_p] * 12 + [ctypes.c_int64] * 6 + [ctypes.c_double] + [ctypes.c_int64] * 10 + [ctypes.c_void_p],
     # returns the mode (1 direct output, 0 split + workspace), not an error code
     "prime_flash_bwd_dkv_direct": [ctypes.c_int64] * 6,
     "prime_mfma_probe": [ctypes.c_void_p] * 4,

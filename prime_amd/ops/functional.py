@@ -7,6 +7,8 @@ works without a GPU.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import reference as ref
@@ -420,8 +422,6 @@ class _FlashAttention(torch.autograd.Function):
         # fp32 partial each. Direct: one block walks the same slices itself
         # and adds them up in the same order (same bits), parking the
         # running sum in a single slice of workspace — none for one slice.
-        import os
-
         direct = bool(lib().prime_flash_bwd_dkv_direct(
             B, Hkv, S, D, int(causal), int(doc_end is not None)))
         env = os.environ.get("PRIME_AMD_DKV_SPLITS")
@@ -439,7 +439,7 @@ class _FlashAttention(torch.autograd.Function):
         check(
             lib().prime_flash_bwd_dkv(
                 stream_of(q), ptr(q), ptr(qt), ptr(k), ptr(v), ptr(do),
-                ptr(dot), ptr(lse), ptr(delta), ptr(rowc), ptr(dk), ptr(dv),
+                ptr(dot), ptr(rowc), ptr(dk), ptr(dv),
                 ptr(None if ws is None else ws[0]), ptr(None if ws is None else ws[1]), splits,
                 B, H, Hkv, S, D, scale, int(causal),
                 q.stride(0), q.stride(1), q.stride(2),
