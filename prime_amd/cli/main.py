@@ -686,6 +686,19 @@ def eval_cmd(
                    f"({res['tokens']:,} tokens)")
 
 
+def _kv_dtype_option(value: str) -> str:
+    from ..models.generate import KV_DTYPES
+
+    if value not in KV_DTYPES:
+        raise typer.BadParameter(f"choose from {', '.join(KV_DTYPES)}")
+    return value
+
+
+_KV_DTYPE_HELP = ("KV cache storage of the ragged decode path: bf16, or fp8 "
+                  "(e4m3 bytes + one fp32 scale per row and kv head, half "
+                  "the memory)")
+
+
 # --------------------------------------------------------------- generate
 @app.command("generate")
 def generate_cmd(
@@ -700,6 +713,9 @@ def generate_cmd(
     top_k: int = typer.Option(0),
     seed: int = typer.Option(0),
     checkpoint: Optional[str] = typer.Option(None, help="checkpoint dir (latest tag)"),
+    kv_dtype: str = typer.Option("bf16", "--kv-dtype", callback=_kv_dtype_option,
+                                 help=_KV_DTYPE_HELP + "; with fp8 a single "
+                                 "prompt runs as a ragged batch of one"),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch
@@ -734,26 +750,27 @@ def generate_cmd(
             raise typer.Exit(2)
         from ..utils.tokenizer import encode
 
-        ids = encode(tok, prompt)
+        prompts = [encode(tok, prompt)]
     else:
         groups = [g for pt in prompt_tokens for g in pt.split(";") if g.strip()]
         prompts = [[int(t) for t in g.split(",")] for g in groups]
-        if len(prompts) > 1:
-            # several prompts of different lengths: one ragged batch, one
-            # output line (the new tokens) per prompt
-            from ..models.generate import generate_batch
+    if len(prompts) > 1 or kv_dtype != "bf16":
+        # several prompts of different lengths: one ragged batch, one output
+        # line (prompt + new tokens) per prompt; the fp8 cache exists on the
+        # ragged path only, so it takes a single prompt this way too
+        from ..models.generate import generate_batch
 
-            outs = generate_batch(m, prompts, max_new, temperature=temperature,
-                                  top_k=top_k, seed=seed)
-            for p_ids, new in zip(prompts, outs):
-                if tok is not None:
-                    from ..utils.tokenizer import decode as tok_decode
+        outs = generate_batch(m, prompts, max_new, temperature=temperature,
+                              top_k=top_k, seed=seed, kv_dtype=kv_dtype)
+        for p_ids, new in zip(prompts, outs):
+            if tok is not None:
+                from ..utils.tokenizer import decode as tok_decode
 
-                    typer.echo(tok_decode(tok, p_ids + new))
-                else:
-                    typer.echo(",".join(str(t) for t in p_ids + new))
-            return
-        ids = prompts[0]
+                typer.echo(tok_decode(tok, p_ids + new))
+            else:
+                typer.echo(",".join(str(t) for t in p_ids + new))
+        return
+    ids = prompts[0]
     toks = torch.tensor([ids], device=dev)
     out = generate(m, toks, max_new, temperature=temperature, top_k=top_k,
                    seed=seed)
@@ -903,6 +920,8 @@ def serve_cmd(
                                   "decode batch (1 = one request per call)"),
     batch_window_ms: float = typer.Option(5.0, help="how long the first "
                                           "waiting request waits for company"),
+    kv_dtype: str = typer.Option("bf16", "--kv-dtype", callback=_kv_dtype_option,
+                                 help=_KV_DTYPE_HELP),
 ):
     """Serve the model over an OpenAI-style HTTP API (engine-side
     counterpart of the reference's hosted inference surface):
@@ -923,7 +942,7 @@ def serve_cmd(
         raise typer.Exit(1)
     secho(f"serving {model} on http://{host}:{port} (ctrl-c to stop)", fg="green")
     uvicorn.run(create_app(m, model, tok, max_batch=max_batch,
-                           batch_window_ms=batch_window_ms),
+                           batch_window_ms=batch_window_ms, kv_dtype=kv_dtype),
                 host=host, port=port,
                 log_level="warning")
 

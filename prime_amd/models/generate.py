@@ -14,7 +14,10 @@ from __future__ import annotations
 
 import torch
 
+from .. import ops
 from .llama import Llama
+
+KV_DTYPES = ("bf16", "fp8")
 
 
 def _pad64(n: int) -> int:
@@ -176,6 +179,7 @@ def generate_batch(
     seed=None,
     stop_token_ids=None,
     use_graph: bool = True,
+    kv_dtype: str = "bf16",
 ) -> list[list[int]]:
     """Ragged batched generation: `prompts` is a list of token-id lists of
     different lengths; returns the NEW tokens of each. max_new_tokens,
@@ -191,8 +195,17 @@ def generate_batch(
     pos[b] before attending to pos[b] + 1 rows), then one ragged decode pass
     per token. The batch is padded with idle slots to a power of two; with
     use_graph on CUDA the per-token pass is a hipGraph captured once per
-    (batch bucket, cache-length bucket, device) that advances its own
-    device-side positions."""
+    (batch bucket, cache-length bucket, device, kv_dtype) that advances its
+    own device-side positions.
+
+    kv_dtype "bf16" keeps the cache in the model's dtype; "fp8" stores it as
+    e4m3 bytes with one fp32 scale per (row, kv head) (ops.KVCacheFp8): half
+    the memory and traffic. The prefill attends to the unquantised k and v,
+    so the first new token is that of the bf16 cache; later tokens see the
+    quantised rows."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got "
+                         f"{kv_dtype!r})")
     model.eval()
     cfg = model.cfg
     p0 = next(model.parameters())
@@ -228,16 +241,20 @@ def generate_batch(
     sessions = getattr(model, "_decode_sessions", None)
     if sessions is None:
         sessions = model._decode_sessions = {}
-    key = ("ragged", Bk, smax, dev.index)
+    key = ("ragged", Bk, smax, dev.index, kv_dtype)
     sess = sessions.get(key) if graphing else None
     if sess is None:
-        caches = [
-            (
-                torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
-                torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
-            )
-            for _ in range(cfg.n_layers)
-        ]
+        if kv_dtype == "fp8":
+            caches = [ops.kv_cache_fp8(Bk, smax, cfg.n_kv_heads, cfg.head_dim, dev)
+                      for _ in range(cfg.n_layers)]
+        else:
+            caches = [
+                (
+                    torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
+                    torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
+                )
+                for _ in range(cfg.n_layers)
+            ]
         sess = _ragged_state(caches, Bk, dev)
         if graphing:
             # capture BEFORE prefill, as _build_session does: the warmup and
@@ -277,7 +294,8 @@ def generate_batch(
     for b in range(n):
         padded[b, :L0[b]] = torch.tensor(prompts[b], dtype=torch.int64)
     padded = padded.to(dev)
-    pre = [(kc[:n], vc[:n]) for kc, vc in caches]
+    pre = [ops.KVCacheFp8(*(t[:n] for t in c)) if isinstance(c, ops.KVCacheFp8)
+           else (c[0][:n], c[1][:n]) for c in caches]
     h = model(padded, caches=pre, pos=0)
     last = torch.tensor([l - 1 for l in L0], device=dev)
     logits = model.lm_head(h[torch.arange(n, device=dev), last])

@@ -71,8 +71,14 @@ class Attention(nn.Module):
                     or self.sp_group is not None:
                 raise ValueError("seq_pos cannot be combined with doc_start, "
                                  "pos_dev or sequence parallelism")
-            kc, vc = cache
             qkv = self.wqkv(x).view(B, -1)
+            if isinstance(cache, ops.KVCacheFp8):
+                q = ops.decode_qkv_append_fp8(qkv, cos, sin, cache,
+                                              seq_pos["pos"], cfg.n_heads,
+                                              cfg.n_kv_heads)
+                o = ops.attn_decode_ragged_fp8(q, cache, seq_pos["lens"])
+                return self.wo(o.reshape(B, 1, cfg.n_heads * hd))
+            kc, vc = cache
             q = ops.decode_qkv_append(qkv, cos, sin, kc, vc, seq_pos["pos"],
                                       cfg.n_heads, cfg.n_kv_heads)
             o = ops.attn_decode_ragged(q, kc, vc, seq_pos["lens"])
@@ -99,6 +105,12 @@ class Attention(nn.Module):
                 o = ops.flash_attention(q, k, v, causal=True,
                                         doc_start=doc_start)
             return self.wo(o.reshape(B, S, cfg.n_heads * hd))
+        fp8_cache = isinstance(cache, ops.KVCacheFp8)
+        if fp8_cache and (S == 1 or pos_dev is not None):
+            # the single-position decode paths run the older one-length
+            # kernel, which reads a bf16 cache
+            raise ValueError("an fp8 KV cache decodes through the ragged "
+                             "kernels only (seq_pos): use generate_batch")
         qkv = self.wqkv(x)
         q, k, v = qkv.split(
             [cfg.n_heads * hd, cfg.n_kv_heads * hd, cfg.n_kv_heads * hd], dim=-1
@@ -109,6 +121,12 @@ class Attention(nn.Module):
         p32 = pos_dev["pos32"] if pos_dev is not None else None
         q = ops.apply_rope(q, cos, sin, pos_offset=pos, pos_dev=p32)
         k = ops.apply_rope(k, cos, sin, pos_offset=pos, pos_dev=p32)
+        if fp8_cache:
+            # prefill: store quantised, attend to the unquantised k, v (the
+            # prefill logits are those of the bf16-cache path)
+            ops.kv_store_fp8(cache, k, v, pos)
+            o = ops.flash_attention(q, k, v, causal=True)
+            return self.wo(o.reshape(B, S, cfg.n_heads * hd))
         if cache is not None:
             kc, vc = cache  # [B, Smax, Hkv, hd]
             if pos_dev is not None:  # graph-capturable dynamic position
@@ -211,7 +229,8 @@ class Llama(nn.Module):
     def forward(self, tokens: torch.Tensor, caches=None, pos: int = 0,
                 pos_dev=None, doc_start=None, seq_pos=None) -> torch.Tensor:
         """tokens [B,S] -> hidden states [B,S,dim] (pre-lm_head).
-        caches: optional per-layer (k,v) KV caches for inference; pos_dev:
+        caches: optional per-layer (k,v) KV caches for inference, or
+        ops.KVCacheFp8 (prefill and seq_pos decode only); pos_dev:
         device-scalar position dict for hipGraph-captured decode.
         seq_pos: ragged batched decode, a dict of int32 [B] device tensors
         {"pos": position of each sequence's new token (negative = idle slot),

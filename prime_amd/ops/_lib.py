@@ -50,6 +50,9 @@ _SIGS = {
     "prime_attn_decode_ragged": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 6 + [ctypes.c_double],
     "prime_decode_ragged_chunk": [],
     "prime_decode_qkv_append": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 6,
+    "prime_attn_decode_ragged_fp8": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 6 + [ctypes.c_double],
+    "prime_decode_qkv_append_fp8": [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 6,
+    "prime_kv_store_fp8": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 6,
     "prime_gemm_nt": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 4,
     "prime_gemm_nt8": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 4,
     "prime_quant_fp8": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 2,

@@ -8,6 +8,7 @@ works without a GPU.
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -1296,6 +1297,200 @@ def decode_qkv_append(qkv, cos, sin, k_cache, v_cache, pos, n_heads: int,
         "decode_qkv_append",
     )
     return q
+
+
+# ------------------------------------------------------------ fp8 KV cache
+class KVCacheFp8(NamedTuple):
+    """One layer's fp8 KV cache. k, v: float8_e4m3fn [B,Smax,Hkv,D];
+    k_scale, v_scale: fp32 [B,Smax,Hkv], the dequantisation factor of each
+    (sequence, row, kv head) vector. For a vector x: m = max(max|x|, 1e-12),
+    s = 448 / m, sinv = m / 448 (fp32), byte = e4m3_rne(clamp(x * s, -448,
+    448)), scale = sinv; the stored value is float(byte) * sinv. A zero
+    vector gives zero bytes and sinv = 1e-12 / 448."""
+    k: torch.Tensor
+    v: torch.Tensor
+    k_scale: torch.Tensor
+    v_scale: torch.Tensor
+
+
+_E4M3_MAX = 448.0
+
+
+def kv_cache_fp8(B: int, Smax: int, Hkv: int, D: int, device=None) -> KVCacheFp8:
+    """A zeroed fp8 KV cache for one layer."""
+    def z(*shape, dtype):
+        return torch.zeros(*shape, dtype=dtype, device=device)
+
+    return KVCacheFp8(z(B, Smax, Hkv, D, dtype=torch.float8_e4m3fn),
+                      z(B, Smax, Hkv, D, dtype=torch.float8_e4m3fn),
+                      z(B, Smax, Hkv, dtype=torch.float32),
+                      z(B, Smax, Hkv, dtype=torch.float32))
+
+
+def kv_cache_dequant(cache: KVCacheFp8):
+    """The values an fp8 cache holds, as fp32 (k, v) [B,Smax,Hkv,D]: the
+    executable definition of the format."""
+    return (cache.k.float() * cache.k_scale.unsqueeze(-1),
+            cache.v.float() * cache.v_scale.unsqueeze(-1))
+
+
+def _kv_quant(x: torch.Tensor):
+    """x [..., D] -> (e4m3 [..., D], sinv fp32 [...]) by the KVCacheFp8 rule,
+    in plain torch."""
+    xf = x.float()
+    m = xf.abs().amax(dim=-1, keepdim=True).clamp(min=1e-12)
+    fm = torch.tensor(_E4M3_MAX, dtype=torch.float32, device=x.device)
+    q = (xf * (fm / m)).clamp(-_E4M3_MAX, _E4M3_MAX)
+    return q.to(torch.float8_e4m3fn), (m / fm).squeeze(-1)
+
+
+def _check_fp8_cache(cache, what: str) -> None:
+    if not isinstance(cache, KVCacheFp8):
+        raise TypeError(f"{what} needs a KVCacheFp8 (got {type(cache).__name__})")
+    k, v, ks, vs = cache
+    if k.dim() != 4 or v.shape != k.shape or ks.shape != k.shape[:3] \
+            or vs.shape != k.shape[:3]:
+        raise ValueError(f"{what}: inconsistent KVCacheFp8 shapes")
+    if k.dtype != torch.float8_e4m3fn or v.dtype != torch.float8_e4m3fn \
+            or ks.dtype != torch.float32 or vs.dtype != torch.float32:
+        raise ValueError(f"{what}: KVCacheFp8 needs float8_e4m3fn k/v and "
+                         "fp32 scales")
+
+
+def _fp8_cache_contiguous(cache, what: str) -> None:
+    # a view of the leading slots (cache[:n]) is contiguous too
+    if not all(t.is_contiguous() for t in cache):
+        raise ValueError(f"{what} needs a contiguous KVCacheFp8")
+
+
+def kv_store_fp8(cache: KVCacheFp8, k, v, pos: int) -> None:
+    """Prefill store: quantise k, v [B,S,Hkv,D] per head row into rows
+    [pos, pos+S) of the first B sequences of `cache` ([B',Smax,Hkv,D],
+    B <= B'). Other rows and slots are left as they are."""
+    _check_fp8_cache(cache, "kv_store_fp8")
+    Bc, Smax, Hkv, D = cache.k.shape
+    if k.dim() != 4 or v.shape != k.shape or k.shape[2:] != (Hkv, D) \
+            or k.shape[0] > Bc:
+        raise ValueError(f"kv_store_fp8: k/v {tuple(k.shape)} do not fit a "
+                         f"cache {tuple(cache.k.shape)}")
+    B, S = k.shape[:2]
+    if pos < 0 or pos + S > Smax:
+        raise ValueError(f"kv_store_fp8: rows [{pos}, {pos + S}) outside a "
+                         f"cache of {Smax} rows")
+    if B == 0 or S == 0:
+        return
+    if not _is_hip(k):
+        for x, c, sc in ((k, cache.k, cache.k_scale), (v, cache.v, cache.v_scale)):
+            q, sinv = _kv_quant(x)
+            c[:B, pos:pos + S] = q
+            sc[:B, pos:pos + S] = sinv
+        return
+    if D not in (64, 128):
+        raise NotImplementedError(
+            f"kv_store_fp8 needs head_dim in {{64, 128}} (got {D})")
+    _fp8_cache_contiguous(cache, "kv_store_fp8")
+    k, v = k.contiguous(), v.contiguous()
+    check(
+        lib().prime_kv_store_fp8(
+            stream_of(k), ptr(k), ptr(v), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), B, S, Hkv, D, Smax, pos,
+        ),
+        "kv_store_fp8",
+    )
+
+
+def decode_qkv_append_fp8(qkv, cos, sin, cache: KVCacheFp8, pos, n_heads: int,
+                          n_kv_heads: int) -> torch.Tensor:
+    """decode_qkv_append into an fp8 cache: the same inputs, idle rule and
+    rotated q (bit-identical); k (rotated, rounded to qkv's dtype) and v are
+    quantised per head row into row pos[b] of `cache`."""
+    _check_fp8_cache(cache, "decode_qkv_append_fp8")
+    B = qkv.shape[0]
+    H, Hkv = n_heads, n_kv_heads
+    _, Smax, Hkv_c, D = cache.k.shape
+    T = cos.shape[0]
+    if qkv.dim() != 2 or qkv.shape[1] != (H + 2 * Hkv) * D or Hkv_c != Hkv:
+        raise ValueError(f"decode_qkv_append_fp8: qkv {tuple(qkv.shape)} does "
+                         f"not match heads={H}, kv_heads={Hkv}, head_dim={D}")
+    if pos.dtype != torch.int32 or pos.shape != (B,) or pos.device != qkv.device:
+        raise ValueError("pos must be an int32 [B] tensor on qkv's device")
+    if not _is_hip(qkv):
+        q = torch.zeros(B, H, D, dtype=qkv.dtype, device=qkv.device)
+        x = qkv.view(B, 1, H + 2 * Hkv, D)
+        for b, p in enumerate(pos.tolist()):
+            if not 0 <= p < min(Smax, T):
+                continue
+            q[b] = ref.apply_rope(x[b:b + 1, :, :H], cos, sin, p)[0, 0]
+            kq, ks = _kv_quant(
+                ref.apply_rope(x[b:b + 1, :, H:H + Hkv], cos, sin, p)[0, 0])
+            vq, vs = _kv_quant(x[b, 0, H + Hkv:])
+            cache.k[b, p], cache.k_scale[b, p] = kq, ks
+            cache.v[b, p], cache.v_scale[b, p] = vq, vs
+        return q
+    if D not in (64, 128):
+        raise NotImplementedError(
+            f"decode_qkv_append_fp8 needs head_dim in {{64, 128}} (got {D})")
+    _fp8_cache_contiguous(cache, "decode_qkv_append_fp8")
+    qkv = qkv.contiguous()
+    q = torch.empty(B, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_decode_qkv_append_fp8(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), ptr(cos), ptr(sin),
+            ptr(pos), B, H, Hkv, D, Smax, T,
+        ),
+        "decode_qkv_append_fp8",
+    )
+    return q
+
+
+def attn_decode_ragged_fp8(q, cache: KVCacheFp8, lens, split_rows=None) -> torch.Tensor:
+    """attn_decode_ragged over an fp8 cache: the same lens / idle / clamp
+    rules and split_rows contract; the values attended to are
+    kv_cache_dequant(cache)."""
+    _check_fp8_cache(cache, "attn_decode_ragged_fp8")
+    if q.dim() == 4:
+        q = q.squeeze(1)
+    B, H, D = q.shape
+    _, Smax, Hkv, _ = cache.k.shape
+    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != q.device:
+        raise ValueError("lens must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        o = torch.zeros_like(q)
+        for b, n in enumerate(lens.tolist()):
+            n = min(max(n, 0), Smax)
+            if n > 0:
+                kf, vf = kv_cache_dequant(KVCacheFp8(
+                    *(t[b:b + 1, :n] for t in cache)))
+                o[b] = ref.attention(q[b:b + 1].unsqueeze(1), kf, vf,
+                                     causal=False)[0, 0]
+        return o
+    _check_ragged_shape(H, Hkv, D)
+    _fp8_cache_contiguous(cache, "attn_decode_ragged_fp8")
+    if split_rows is None:
+        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % DECODE_RAGGED_CHUNK != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{DECODE_RAGGED_CHUNK} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    G = H // Hkv
+    # the bf16 op's workspace: same shape key, and the ops run in stream order
+    key = (B, Hkv, G, D, nsplit, q.device.index)
+    ws = _RAGGED_WS.get(key)
+    if ws is None:
+        ws = _RAGGED_WS[key] = torch.empty(
+            B * Hkv, nsplit, G * (D + 2), device=q.device, dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_decode_ragged_fp8(
+            stream_of(q), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), ptr(o), ptr(ws), ptr(lens),
+            B, H, Hkv, Smax, D, split_rows, D**-0.5,
+        ),
+        "attn_decode_ragged_fp8",
+    )
+    return o
 
 
 def mfma_probe32(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:

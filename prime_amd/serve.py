@@ -53,13 +53,16 @@ class ChatRequest(BaseModel):
 
 
 def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
-               batch_window_ms: float = 5.0):
+               batch_window_ms: float = 5.0, kv_dtype: str = "bf16"):
     from fastapi import FastAPI, HTTPException
 
     from .models import generate as gen_mod
 
     if max_batch < 1:
         raise ValueError("max_batch must be >= 1")
+    if kv_dtype not in gen_mod.KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {gen_mod.KV_DTYPES} (got "
+                         f"{kv_dtype!r})")
     app = FastAPI(title="prime-amd inference")
     dev = next(model.parameters()).device
     pending: queue.Queue = queue.Queue()
@@ -82,7 +85,7 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                     temperature=[r.temperature for _, r, _ in items],
                     top_k=[r.top_k for _, r, _ in items],
                     seed=[r.seed for _, r, _ in items],
-                    stop_token_ids=list(stop))
+                    stop_token_ids=list(stop), kv_dtype=kv_dtype)
                 for (_, _, fut), new in zip(items, outs):
                     fut.set_result(new)
             except Exception as e:  # noqa: BLE001 - reported to every caller
@@ -164,7 +167,8 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
 
     @app.get("/health")
     def health():
-        return {"status": "ok", "model": model_name, "device": str(dev)}
+        return {"status": "ok", "model": model_name, "device": str(dev),
+                "kv_dtype": kv_dtype}
 
     @app.get("/v1/models")
     def models():
