@@ -23,6 +23,8 @@ _SIGS = {
     "prime_rmsnorm_bwd": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 3 + [ctypes.c_double],
     "prime_add_rmsnorm_fwd": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 2 + [ctypes.c_double],
     "prime_add_rmsnorm_bwd": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 3 + [ctypes.c_double],
+    "prime_add_rmsnorm_fwd_generic": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 2 + [ctypes.c_double],
+    "prime_add_rmsnorm_bwd_generic": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 3 + [ctypes.c_double],
     "prime_rope": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 4 + [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p],
     "prime_rope_strided": [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 7,
     "prime_qkv_grad_pack": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 6,
@@ -40,6 +42,7 @@ _SIGS = {
     "prime_flash_fwd": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 5 + [ctypes.c_double] + [ctypes.c_int64] * 7 + [ctypes.c_void_p],
     "prime_flash_bwd_dq": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 5 + [ctypes.c_double] + [ctypes.c_int64] * 10 + [ctypes.c_void_p],
     "prime_attn_delta_t": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 4,
+    "prime_attn_delta_dot": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 4,
     "prime_flash_bwd_dkv": [ctypes.c_void_p] * 12 + [ctypes.c_int64] * 6 + [ctypes.c_double] + [ctypes.c_int64] * 10 + [ctypes.c_void_p],
     # returns the mode (1 direct output, 0 split + workspace), not an error code
     "prime_flash_bwd_dkv_direct": [ctypes.c_int64] * 6,

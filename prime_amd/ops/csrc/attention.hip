@@ -548,6 +548,100 @@ __global__ void attn_delta_kernel(const bf16* __restrict__ dO,
   }
 }
 
+// ----------------------------- delta, row constants and dO^T in one pass
+// One block per (b, 64-token tile, h), h fastest so that neighbouring
+// blocks read neighbouring 2*D-byte rows. dO and O are read once, in
+// 16-byte loads; a row is spread over D/8 adjacent lanes. dO goes through a
+// padded LDS tile and leaves as dOt [B,H,D,S] in 16-byte stores (as
+// transpose_bshd_kernel does it); lse^T and delta^T leave as 64 consecutive
+// floats each; delta [B,S,H] is still written for the dQ kernels.
+//
+// delta has the bits of attn_delta_kernel. There lane L of a wave holds
+// p_L = dO[2L]*O[2L] + dO[2L+1]*O[2L+1] (zero for 2L >= D) and
+// wave_reduce_sum pairs L with L+32, L+16, ..., L+1. Here lane m of a row
+// holds p_{4m..4m+3}, so the same tree is: m with m+8 (at D = 64: with the
+// zeros of the absent upper half), m+4, m+2, m+1 component by component,
+// then components {0,2} and {1,3}, then those two.
+template <int D>
+__global__ __launch_bounds__(256) void attn_delta_dot_kernel(
+    const bf16* __restrict__ dO, const bf16* __restrict__ O,
+    const float* __restrict__ lse, float* __restrict__ delta,
+    float* __restrict__ rowc_t, bf16* __restrict__ dOt, int S, int H,
+    int64_t rows) {
+  constexpr int LPR = D / 8;      // lanes per row
+  constexpr int RPP = 256 / LPR;  // rows per pass
+  constexpr int NP = 64 / RPP;    // passes over the 64-row tile
+  constexpr int TPD = D + 8;      // padded LDS row, keeps 16-byte alignment
+  __shared__ __attribute__((aligned(16))) bf16 tile[64][TPD];
+  __shared__ float sdelta[64];
+  int idx = blockIdx.x;
+  const int h = idx % H; idx /= H;
+  const int n_st = S / 64;
+  const int st = idx % n_st;
+  const int b = idx / n_st;
+  const int t = threadIdx.x;
+  const int m = t % LPR, rr = t / LPR;
+  const int64_t tok0 = (int64_t)b * S + st * 64;   // first token of the tile
+  const int64_t tcol = ((int64_t)b * H + h) * S + st * 64;  // same, [B,H,S]
+
+  short8 vdo[NP], vo[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int64_t off = ((tok0 + p * RPP + rr) * H + h) * D + m * 8;
+    vdo[p] = *reinterpret_cast<const short8*>(dO + off);
+    vo[p] = *reinterpret_cast<const short8*>(O + off);
+  }
+  float lv = 0.f;
+  if (t >= 64 && t < 128) lv = lse[(tok0 + (t - 64)) * H + h];
+
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int row = p * RPP + rr;
+    *reinterpret_cast<short8*>(&tile[row][m * 8]) = vdo[p];
+    const bf16* a = reinterpret_cast<const bf16*>(&vdo[p]);
+    const bf16* c = reinterpret_cast<const bf16*>(&vo[p]);
+    float q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float acc = 0.f;
+      acc += bf2f(a[2 * i]) * bf2f(c[2 * i]);
+      acc += bf2f(a[2 * i + 1]) * bf2f(c[2 * i + 1]);
+      q[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (D == 64) q[i] = q[i] + 0.f;
+      else q[i] += __shfl_down(q[i], 8, 64);
+    }
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) q[i] += __shfl_down(q[i], off, 64);
+    if (m == 0) sdelta[row] = (q[0] + q[2]) + (q[1] + q[3]);
+  }
+  __syncthreads();
+  if (t < 64) {
+    const float d = sdelta[t];
+    delta[(tok0 + t) * H + h] = d;
+    rowc_t[rows + tcol + t] = d;
+  } else if (t < 128) {
+    rowc_t[tcol + (t - 64)] = lv;
+  }
+  // dOt rows d = 0..D-1, 64 tokens each: D*8 16-byte units
+  bf16* dbase = dOt + ((int64_t)b * H + h) * D * S + st * 64;
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i) {
+    const int u = i * 256 + t;
+    const int d = u >> 3, s8 = (u & 7) * 8;
+    short8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      reinterpret_cast<short*>(&v)[j] =
+          reinterpret_cast<const short*>(&tile[s8 + j][d])[0];
+    *reinterpret_cast<short8*>(dbase + (int64_t)d * S + s8) = v;
+  }
+}
+
 // ------------------------------------------------ backward dQ v5 (32x32)
 // Same 8-wave swapped-operand structure as the v5 forward: St = K·Q^T and
 // dPt = V·dO^T give lane-local q-rows (q = lane&31), so lse/delta are one
@@ -1136,6 +1230,32 @@ PRIME_API int prime_attn_delta_t(hipStream_t stream, const void* dO,
   hipLaunchKernelGGL(attn_delta_kernel, dim3(grid), dim3(256), 0, stream,
                      (const bf16*)dO, (const bf16*)O, (float*)delta, rows,
                      (int)D, (const float*)lse, (float*)rowc_t, (int)S, (int)H);
+  return (int)hipGetLastError();
+}
+
+// The same delta and rowc_t, plus dOt [B,H,D,S] = dO^T, in one pass over
+// contiguous dO and O [B,S,H,D] (replaces prime_attn_delta_t followed by a
+// transpose of dO).
+PRIME_API int prime_attn_delta_dot(hipStream_t stream, const void* dO,
+                                   const void* O, const void* lse, void* delta,
+                                   void* rowc_t, void* dOt, int64_t B,
+                                   int64_t S, int64_t H, int64_t D) {
+  if (!dO || !O || !lse || !delta || !rowc_t || !dOt) return hipErrorInvalidValue;
+  if (S % 64 != 0 || (D != 64 && D != 128)) return hipErrorInvalidValue;
+  const int64_t rows = B * S * H;
+  const int64_t grid = B * H * (S / 64);
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if (grid == 0) return (int)hipSuccess;
+  if (D == 64)
+    hipLaunchKernelGGL(attn_delta_dot_kernel<64>, dim3((int)grid), dim3(256), 0,
+                       stream, (const bf16*)dO, (const bf16*)O,
+                       (const float*)lse, (float*)delta, (float*)rowc_t,
+                       (bf16*)dOt, (int)S, (int)H, rows);
+  else
+    hipLaunchKernelGGL(attn_delta_dot_kernel<128>, dim3((int)grid), dim3(256),
+                       0, stream, (const bf16*)dO, (const bf16*)O,
+                       (const float*)lse, (float*)delta, (float*)rowc_t,
+                       (bf16*)dOt, (int)S, (int)H, rows);
   return (int)hipGetLastError();
 }
 

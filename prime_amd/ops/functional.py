@@ -396,10 +396,12 @@ class _FlashAttention(torch.autograd.Function):
         delta = torch.empty(B * S * H, device=q.device, dtype=torch.float32)
         # rowc = {lse, delta} again in [B,H,S] order, for the dK/dV kernel
         rowc = torch.empty(2, B, H, S, device=q.device, dtype=torch.float32)
+        # the same pass over dO also writes dO^T [B,H,D,S] for dK/dV
+        dot = torch.empty(B, H, D, S, device=q.device, dtype=q.dtype)
         check(
-            lib().prime_attn_delta_t(stream_of(q), ptr(do), ptr(o), ptr(lse), ptr(delta),
-                                     ptr(rowc), B, S, H, D),
-            "attn_delta",
+            lib().prime_attn_delta_dot(stream_of(q), ptr(do), ptr(o), ptr(lse), ptr(delta),
+                                       ptr(rowc), ptr(dot), B, S, H, D),
+            "attn_delta_dot",
         )
         kt = transpose_bshd(k)  # [B,Hkv,D,S]
         dq = torch.empty(B, S, H, D, device=q.device, dtype=q.dtype)
@@ -415,7 +417,6 @@ class _FlashAttention(torch.autograd.Function):
             "flash_bwd_dq",
         )
         qt = transpose_bshd(q)   # [B,H,D,S]
-        dot = transpose_bshd(do)
         dk = torch.empty(B, S, Hkv, D, device=q.device, dtype=q.dtype)
         dv = torch.empty(B, S, Hkv, D, device=q.device, dtype=q.dtype)
         # the library picks the mode (see prime_flash_bwd_dkv_direct). Split:
