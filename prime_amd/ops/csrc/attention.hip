@@ -100,6 +100,14 @@ __device__ __forceinline__ void st16_swz(bf16* lds_tile, int row, int col,
                            ((col * 2) ^ ((row & 7) << 4))) = v;
 }
 
+// two adjacent columns (col even) of one row as one 4-byte store
+template <int COLS>
+__device__ __forceinline__ void st32_swz(bf16* lds_tile, int row, int col,
+                                         unsigned v) {
+  *reinterpret_cast<unsigned*>(reinterpret_cast<char*>(lds_tile) + row * (COLS * 2) +
+                               ((col * 2) ^ ((row & 7) << 4))) = v;
+}
+
 // wave-local fence: P/dS LDS writes must land before same-wave ld8 reads
 __device__ __forceinline__ void wave_lds_fence() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -311,6 +319,11 @@ __device__ __forceinline__ void permlane32_swap(unsigned& a, unsigned& b) {
   asm volatile("v_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
+// the value of lane l^1 (DPP quad_perm [1,0,3,2]; every lane active)
+__device__ __forceinline__ unsigned lane_xor1(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0xB1, 0xF, 0xF, false);
+}
+
 template <int D, bool DOC = false>
 __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -419,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
     if (DOC && kv < my_ds_last) {  // wave-uniform: a boundary tile
       // a row still wholly masked keeps m_run = NEG_INF through the
       // per-wave rescale below (alpha = exp(0) = 1 on o = l = 0) and
-      // p = 0 through the <= NEG_INF guard, so nothing leaks
+      // p = 0 through m_sub below, so nothing leaks
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -428,14 +441,22 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
           if (kg < my_ds) st[t][r] = NEG_INF;
         }
     }
+    if (causal && kv + 63 > q0w) {  // wave-uniform: the diagonal tile
+      // the only computed tile that can hold a key past a row of this
+      // wave: later tiles are skipped above, earlier ones end at or
+      // before q0w
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kg = kv + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          if (kg > q0w + lo) st[t][r] = NEG_INF;
+        }
+    }
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int kg = kv + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (causal && kg > q0w + lo) st[t][r] = NEG_INF;
-        tmax = fmaxf(tmax, st[t][r]);
-      }
+      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[t][r]);
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
     // defer-max (guide T13): skip the O-wide rescale while the running
     // max still bounds P by e^THR (fp32 accumulation tolerates it)
@@ -453,12 +474,22 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
         for (int r = 0; r < 16; ++r)
           o_acc[dt][r] *= bcast[(r & 3) + 8 * (r >> 2) + 4 * hi];
     }
+    // A masked score needs no select of its own: once a row has seen one
+    // visible key m_run is finite, and exp(NEG_INF - m_run) is 0 by
+    // itself. Without a document mask that holds from the first computed
+    // tile on (it holds key 0, or every key when not causal). With one, a
+    // row can reach a tile before its document starts with m_run still
+    // NEG_INF; all its scores there are NEG_INF too, so subtracting 0 in
+    // place of m_run gives the same 0. (An unmasked score at or below
+    // NEG_INF would need |q.k| >= 1e30.)
+    float m_sub = m_run;
+    if (DOC && m_run <= NEG_INF) m_sub = 0.f;
     float psum = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pv = (st[t][r] <= NEG_INF) ? 0.f : __expf(st[t][r] - m_run);
+        const float pv = __expf(st[t][r] - m_sub);
         st[t][r] = pv;
         psum += pv;
       }
@@ -751,6 +782,22 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
         dpt[t] = mfma32(vf, dof[ds], dpt[t]);
       }
     }
+    // ---- causal mask, on the wave's diagonal tile only (wave-uniform; no
+    // other computed tile holds a key past one of its rows). A masked
+    // score becomes NEG_INF, and exp(NEG_INF - lse) is the same +0 the
+    // select on p gave: lse is finite, every row sees its own key. The
+    // document-mask instantiation keeps both selects inline on every tile:
+    // with this branch it needs 256 VGPRs plus scratch at D = 128 and
+    // loses a wave per SIMD at D = 64.
+    if (!DOC && causal && kv + 63 > q0w) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kg = kv + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          if (kg > q0w + lo) st[t][r] = NEG_INF;
+        }
+    }
     // ---- dS = P * (dP - delta) * scale, all in-register (q = lo)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -758,7 +805,7 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
       for (int r = 0; r < 16; ++r) {
         const int kg = kv + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float p = __expf(st[t][r] - lse_q);
-        if (causal && kg > q0w + lo) p = 0.f;
+        if (DOC && causal && kg > q0w + lo) p = 0.f;
         if (DOC && kg < my_ds) p = 0.f;
         st[t][r] = p * (dpt[t][r] - dl_q) * scale;
       }
@@ -916,11 +963,11 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
 // Qt[D][64] and dOt[D][64] (operands of the dK and dV accumulation).
 //
 // Tile body: St = mfma16(kf, qb) leaves the key on the accumulator row, so
-// each wave passes P and dS through its own LDS buffers (2-byte swizzled
-// stores, a wave-local fence, 16-byte reads) to get them key-on-the-lane
-// for dV += P^T·dO and dK += dS^T·Q. At NW=8, D=128, DBUF=2 that is
-// 2x4x16 KiB stages + 8x2x2 KiB wave buffers = exactly the 160 KiB LDS
-// limit. acc[dt][r] = [k0 + lg*4 + r][dt*16 + li]. Keeping P and dS in
+// each wave passes P and dS through its own LDS buffers (4-byte swizzled
+// stores of column pairs, a wave-local fence, 16-byte reads) to get them
+// key-on-the-lane for dV += P^T·dO and dK += dS^T·Q. At NW=8, D=128,
+// DBUF=2 that is 2x4x16 KiB stages + 8x2x2 KiB wave buffers = exactly the
+// 160 KiB LDS limit. acc[dt][r] = [k0 + lg*4 + r][dt*16 + li]. Keeping P and dS in
 // registers instead (key on the lane from the start) and a 32x32 variant
 // both measured slower: docs/KERNELS.md.
 //
@@ -1082,15 +1129,36 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
         const int64_t o = (int64_t)(hkv * group + g) * S + qg;
         const float lse_q = lse_t[o];
         const float dl_q = dl_t[o];
+        float pv[4], dsv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float p = __expf(st_acc[r] * scale - lse_q);
           if (causal && k0 + lg * 4 + r > qg) p = 0.f;
           if (DOC && qg >= key_end4[r]) p = 0.f;
-          st16_swz<64>(pt_lds, lg * 4 + r, sub * 16 + li, f2bf(p));
-          st16_swz<64>(dst_lds, lg * 4 + r, sub * 16 + li,
-                       f2bf(p * (dpt_acc[r] - dl_q) * scale));
+          pv[r] = p;
+          dsv[r] = p * (dpt_acc[r] - dl_q) * scale;
         }
+        // Lanes li and li^1 hold adjacent query columns of the same four
+        // key rows. The even lane hands over rows 2-3 and takes rows 0-1
+        // of the pair's two columns, the odd lane the reverse, so each
+        // lane stores two 4-byte column pairs per buffer where it stored
+        // four bf16: the same bytes at the same swizzled addresses (the
+        // XOR moves 16-byte units, a column pair stays together).
+        const unsigned p01 = cvt_pk_bf16(pv[0], pv[1]), p23 = cvt_pk_bf16(pv[2], pv[3]);
+        const unsigned d01 = cvt_pk_bf16(dsv[0], dsv[1]), d23 = cvt_pk_bf16(dsv[2], dsv[3]);
+        const int odd = li & 1;
+        const unsigned pgot = lane_xor1(odd ? p01 : p23);
+        const unsigned dgot = lane_xor1(odd ? d01 : d23);
+        const unsigned pown = odd ? p23 : p01, down = odd ? d23 : d01;
+        // v_perm_b32 byte selectors, 0-3 from own and 4-7 from got: the
+        // lower column comes first, and that is the even lane's
+        const unsigned sel0 = odd ? 0x01000504u : 0x05040100u;  // first row of the two
+        const unsigned sel1 = odd ? 0x03020706u : 0x07060302u;  // second row
+        const int prow = lg * 4 + 2 * odd, pcol = sub * 16 + (li & ~1);
+        st32_swz<64>(pt_lds, prow, pcol, __builtin_amdgcn_perm(pgot, pown, sel0));
+        st32_swz<64>(pt_lds, prow + 1, pcol, __builtin_amdgcn_perm(pgot, pown, sel1));
+        st32_swz<64>(dst_lds, prow, pcol, __builtin_amdgcn_perm(dgot, down, sel0));
+        st32_swz<64>(dst_lds, prow + 1, pcol, __builtin_amdgcn_perm(dgot, down, sel1));
       }
       wave_lds_fence();
 #pragma unroll
