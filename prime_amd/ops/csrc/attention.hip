@@ -12,8 +12,9 @@
 //    __builtin_amdgcn_global_load_lds width-16 (no VGPR round trip), with
 //    the T2 XOR-16B swizzle applied via the pre-swizzled SOURCE address
 //    (global_load_lds writes linearly: guide §5.5 T2 + rule 21).
-//  - all operand-fragment LDS reads are ld8 (16 B) at the swizzled address:
-//    2-way bank aliasing max (free on CDNA4).
+//  - all operand-fragment LDS reads are ld8 (16 B) at the swizzled address,
+//    conflict-free under the gfx950 rule (64 banks, 16-lane groups: see
+//    swz16 below).
 //  - per-wave P / dS buffers are swizzled the same way (v1 left a 16-way
 //    conflict on the PV A-fragment reads).
 //  - kernels are STRIDE-AWARE over [B,S,H,D] inputs: q/k/v are consumed
@@ -62,10 +63,61 @@ __device__ __forceinline__ float grp16_sum(float x) {
 
 // ---- swizzled-tile helpers --------------------------------------------
 // A [ROWS][COLS] bf16 tile lives linearly in LDS; byte (row, colb) is
-// stored at row*COLS*2 + (colb ^ ((row&7)<<4)). Stage from a strided
+// stored at row*COLS*2 + (colb ^ swz16<COLS>(row)). Stage from a strided
 // global matrix; read 8-element fragments at the same swizzle.
+//
+// gfx950 LDS: 64 banks x 4 B, i.e. sixteen 16-byte slots per 256-byte
+// line. A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15,
+// 20-27}, {4-11, 16-19, 28-31}, the same two + 32), one LDS cycle per
+// group when its 16 lanes hit 16 distinct slots; N lanes on one slot cost
+// N cycles — 2-way is NOT free for these reads. The XOR is therefore the
+// index of the row's 256-byte line (mod the row's chunk count): row & 15
+// for 256-byte rows, (row >> 1) & 7 for 128-byte rows, where two rows
+// share a line and the row's parity already picks the half. Every operand
+// read of the kernels below is then conflict-free, and the 4-byte P/dS
+// stores are at most 2-way (free for ds_write_b32):
+// tests/test_attn_swizzle_cpu.py walks each pattern.
+template <int COLS>
+__device__ __forceinline__ int swz16(int row) {
+  static_assert(COLS == 64 || COLS == 128, "128- or 256-byte rows");
+  return (COLS == 128 ? (row & 15) : ((row >> 1) & 7)) << 4;
+}
 
-template <int ROWS, int COLS, int NT = 256>
+// One 16-byte-per-lane LDS-DMA load that the compiler does not track. The
+// builtin form is a pending LDS write in hipcc's wait bookkeeping, so the
+// first ds_read after it gets an s_waitcnt vmcnt(0) even when it reads
+// another buffer, and a prefetch issued behind the barrier lands before
+// the tile's compute starts instead of under it. From inline assembly the
+// load is invisible to that bookkeeping: nothing waits for it but the
+// stage_wait_all() the double-buffered loops place in front of their
+// tile-boundary barrier. M0 (the wave-uniform LDS destination) is
+// compiler-reserved, so it is saved, set and restored in one statement.
+__device__ __forceinline__ void glds16_untracked(const bf16* src, lds_char* dst) {
+  const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane(
+      (int)(__UINTPTR_TYPE__)dst);
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(src), "s"(m0v)
+      : "memory");
+}
+
+// s_waitcnt vmcnt(0): every load this wave issued, LDS-DMA included, has
+// landed. As a builtin (not asm) the compiler's own bookkeeping sees it.
+// gfx9 encoding: vmcnt = imm[15:14]:imm[3:0], expcnt and lgkmcnt left open.
+__device__ __forceinline__ void stage_wait_all() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
+// UNTRACKED: for the double-buffered loops. Their contract, per buffer:
+// written only after the barrier that ends its last read; read only after
+// every issuing wave's stage_wait_all() and the barrier that follows it.
+template <int ROWS, int COLS, int NT = 256, bool UNTRACKED = false>
 __device__ __forceinline__ void stage_tile(const bf16* __restrict__ gbase,
                                            int64_t row_stride, bf16* lds_tile,
                                            int tid) {
@@ -76,12 +128,15 @@ __device__ __forceinline__ void stage_tile(const bf16* __restrict__ gbase,
   for (int i = 0; i < UNITS / NT; ++i) {
     const int u = i * NT + tid;
     const int row = u / UPR;
-    const int colb = ((u % UPR) * 16) ^ ((row & 7) << 4);  // pre-swizzle src
+    const int colb = ((u % UPR) * 16) ^ swz16<COLS>(row);  // pre-swizzle src
     const bf16* src = gbase + (int64_t)row * row_stride + colb / 2;
     // linear dest: wave-uniform base + lane*16 (global_load_lds contract)
     const int wid = tid >> 6;
-    lds_void* dst = (lds_void*)((lds_char*)lds_tile + i * (NT * 16) + wid * 1024);
-    __builtin_amdgcn_global_load_lds((g_void*)src, dst, 16, 0, 0);
+    lds_char* dst = (lds_char*)lds_tile + i * (NT * 16) + wid * 1024;
+    if (UNTRACKED)
+      glds16_untracked(src, dst);
+    else
+      __builtin_amdgcn_global_load_lds((g_void*)src, (lds_void*)dst, 16, 0, 0);
   }
 }
 
@@ -90,14 +145,14 @@ __device__ __forceinline__ short8 ld8_swz(const bf16* lds_tile, int row,
                                           int colb) {
   return *reinterpret_cast<const short8*>(
       reinterpret_cast<const char*>(lds_tile) + row * (COLS * 2) +
-      (colb ^ ((row & 7) << 4)));
+      (colb ^ swz16<COLS>(row)));
 }
 
 template <int COLS>
 __device__ __forceinline__ void st16_swz(bf16* lds_tile, int row, int col,
                                          bf16 v) {
   *reinterpret_cast<bf16*>(reinterpret_cast<char*>(lds_tile) + row * (COLS * 2) +
-                           ((col * 2) ^ ((row & 7) << 4))) = v;
+                           ((col * 2) ^ swz16<COLS>(row))) = v;
 }
 
 // two adjacent columns (col even) of one row as one 4-byte store
@@ -105,7 +160,7 @@ template <int COLS>
 __device__ __forceinline__ void st32_swz(bf16* lds_tile, int row, int col,
                                          unsigned v) {
   *reinterpret_cast<unsigned*>(reinterpret_cast<char*>(lds_tile) + row * (COLS * 2) +
-                               ((col * 2) ^ ((row & 7) << 4))) = v;
+                               ((col * 2) ^ swz16<COLS>(row))) = v;
 }
 
 // wave-local fence: P/dS LDS writes must land before same-wave ld8 reads
@@ -292,8 +347,9 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
 // skipping (T13), cheap P exchange and per-wave causal trip clipping.
 // Measured at the 10B shape: defer-max 417 TF vs 387 without; setprio
 // around the MFMA clusters (T5) lost 1-3 %; a third stage buffer with a
-// counted vmcnt at the tile boundary 401 vs 417 — prefetch-behind-barrier
-// already covers the stage latency.
+// counted vmcnt at the tile boundary 401 vs 417 — taken while the
+// compiler's own vmcnt(0) still drained every prefetch in front of the
+// tile's first read (see glds16_untracked), so it settles nothing now.
 //
 // 32x32x16 fragment maps (HW-verified, test_mfma32_layout_vs_matmul):
 //   A[32][16]: lane holds A[lane&31][(lane>>5)*8 + j]
@@ -334,6 +390,9 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
     const int* __restrict__ doc) {
   constexpr int DSL = D / 16;   // 16-wide d slices for the K dim
   constexpr int DT32 = D / 32;  // 32-wide output d tiles
+  // untracked stage loads, except where they cost a wave per SIMD (the
+  // masked D = 64 instantiation went from 128 to 145 VGPRs with them)
+  constexpr bool UT = !(DOC && D == 64);
   const int n_qt = S / 256;
   // XCD-aware bijective remap (guide T1): consecutive qt-tiles of one
   // (b,h) land on ONE XCD's L2, which then reuses the same K/V stream
@@ -397,34 +456,59 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v5_kernel(
     my_ds = doc_b[q0w + lo];
     my_ds_last = doc_b[q0w + 31];
   }
-  stage_tile<64, D, 512>(Kb + (int64_t)kv_begin * sks, sks, k_lds[0], threadIdx.x);
-  stage_tile<D, 64, 512>(Vtb + kv_begin, S, vt_lds[0], threadIdx.x);
+  stage_tile<64, D, 512, UT>(Kb + (int64_t)kv_begin * sks, sks, k_lds[0], threadIdx.x);
+  stage_tile<D, 64, 512, UT>(Vtb + kv_begin, S, vt_lds[0], threadIdx.x);
   int idx = 0;
   for (int kv = kv_begin, kt = 0; kv < kv_end; kv += 64, ++kt) {
     idx = kt % 2;
-    __syncthreads();  // prev tile consumed + this tile's stage drained
+    // tile boundary, reached on every path (the skips below included): this
+    // wave's share of tile kt has landed; behind the barrier everyone's
+    // has, and tile kt-1 is consumed
+    stage_wait_all();
+    __syncthreads();
     if (kv + 64 < kv_end) {
-      // prefetch-behind-barrier: these loads get the whole tile's
-      // compute to land (the next syncthreads drains them)
-      stage_tile<64, D, 512>(Kb + (int64_t)(kv + 64) * sks, sks,
-                             k_lds[(kt + 1) % 2], threadIdx.x);
-      stage_tile<D, 64, 512>(Vtb + kv + 64, S, vt_lds[(kt + 1) % 2],
-                             threadIdx.x);
+      // prefetch-behind-barrier: untracked loads, so no wait stands
+      // between here and the next tile boundary — they get the whole
+      // tile's compute to land
+      stage_tile<64, D, 512, UT>(Kb + (int64_t)(kv + 64) * sks, sks,
+                                 k_lds[(kt + 1) % 2], threadIdx.x);
+      stage_tile<D, 64, 512, UT>(Vtb + kv + 64, S, vt_lds[(kt + 1) % 2],
+                                 threadIdx.x);
     }
     if (kv >= my_kv_end) continue;  // fully-masked tile for this wave
     if (DOC && kv < my_kv_begin) continue;  // before this wave's documents
 
     // ---- St = (K q^T): two 32x32 C tiles over the 64-key block
+    // The K fragments run RING reads ahead of the MFMAs that use them, in
+    // registers of their own, so that no MFMA waits on a read issued
+    // right in front of it (same products, same order).
     f32x16 st[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[t][r] = 0.f;
+    {
+      constexpr int NF = 2 * DSL, RING = 4;
+      short8 kf[RING];
 #pragma unroll
-      for (int ds = 0; ds < DSL; ++ds) {
-        const short8 kf = ld8_swz<D>(k_lds[idx], t * 32 + lo, ds * 32 + hi * 16);
-        st[t] = mfma32(kf, qf[ds], st[t]);
+      for (int i = 0; i < RING; ++i)
+        kf[i] = ld8_swz<D>(k_lds[idx], (i / DSL) * 32 + lo, (i % DSL) * 32 + hi * 16);
+#pragma unroll
+      for (int i = 0; i < NF; ++i) {
+        st[i / DSL] = mfma32(kf[i % RING], qf[i % DSL], st[i / DSL]);
+        if (i + RING < NF)
+          kf[i % RING] = ld8_swz<D>(k_lds[idx], ((i + RING) / DSL) * 32 + lo,
+                                    ((i + RING) % DSL) * 32 + hi * 16);
       }
+      // pin that order: hipcc's scheduler otherwise sinks every read back
+      // in front of its MFMA (0x100 = DS read, 0x008 = MFMA)
+      __builtin_amdgcn_sched_group_barrier(0x100, RING, 0);
+#pragma unroll
+      for (int i = 0; i < NF - RING; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, RING, 0);
     }
     // ---- online softmax: st[t][r] is k = kv + t*32 + crow(r,hi) for
     // q row q0w+lo; lane pair (l, l^32) splits the row's 64 scores
@@ -691,6 +775,12 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
     const int* __restrict__ doc) {
   constexpr int DSL = D / 16;
   constexpr int DT32 = D / 32;
+  // score-loop fragments in registers, and untracked stage loads: what
+  // each instantiation's register class allows (a deeper ring spills at
+  // D = 128; the masked ones lose a wave per SIMD at D = 64 or spill at
+  // D = 128 with untracked loads or a pinned ring)
+  constexpr int DQ_RING = (D == 128 || DOC) ? 2 : 3;
+  constexpr bool UT = !DOC;
   const int n_qt = S / 256;
   const int nwg = gridDim.x;
   int vb = blockIdx.x;
@@ -752,34 +842,60 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dq_v5_kernel(
     my_kv_begin = doc_clamp(doc_b[q0w], q0w) & ~63;
     my_ds = doc_b[q0w + lo];
   }
-  stage_tile<64, D, 512>(Kb + (int64_t)kv_begin * sks, sks, k_lds[0], threadIdx.x);
-  stage_tile<64, D, 512>(Vb + (int64_t)kv_begin * svs, svs, v_lds[0], threadIdx.x);
-  stage_tile<D, 64, 512>(Ktb + kv_begin, S, kt_lds[0], threadIdx.x);
+  stage_tile<64, D, 512, UT>(Kb + (int64_t)kv_begin * sks, sks, k_lds[0], threadIdx.x);
+  stage_tile<64, D, 512, UT>(Vb + (int64_t)kv_begin * svs, svs, v_lds[0], threadIdx.x);
+  stage_tile<D, 64, 512, UT>(Ktb + kv_begin, S, kt_lds[0], threadIdx.x);
   int idx = 0;
   for (int kv = kv_begin; kv < kv_end; kv += 64, idx ^= 1) {
+    // tile boundary as in the v5 forward: own stage landed, then barrier,
+    // on every path; the untracked prefetch then flies under the compute
+    stage_wait_all();
     __syncthreads();
     if (kv + 64 < kv_end) {
-      stage_tile<64, D, 512>(Kb + (int64_t)(kv + 64) * sks, sks,
-                             k_lds[idx ^ 1], threadIdx.x);
-      stage_tile<64, D, 512>(Vb + (int64_t)(kv + 64) * svs, svs,
-                             v_lds[idx ^ 1], threadIdx.x);
-      stage_tile<D, 64, 512>(Ktb + kv + 64, S, kt_lds[idx ^ 1], threadIdx.x);
+      stage_tile<64, D, 512, UT>(Kb + (int64_t)(kv + 64) * sks, sks,
+                                 k_lds[idx ^ 1], threadIdx.x);
+      stage_tile<64, D, 512, UT>(Vb + (int64_t)(kv + 64) * svs, svs,
+                                 v_lds[idx ^ 1], threadIdx.x);
+      stage_tile<D, 64, 512, UT>(Ktb + kv + 64, S, kt_lds[idx ^ 1], threadIdx.x);
     }
     if (kv >= my_kv_end) continue;
     if (DOC && kv < my_kv_begin) continue;
 
     // ---- St = K·Q^T (pre-scaled), dPt = V·dO^T: C[k][q], q = lo
+    // The K and V fragments, taken alternately, run RING - 1 reads ahead
+    // of the MFMAs that use them, as in the v5 forward (same products,
+    // same order). RING is what the register file allows: see the table
+    // in docs/KERNELS.md.
     f32x16 st[2], dpt[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { st[t][r] = 0.f; dpt[t][r] = 0.f; }
+    {
+      constexpr int NF = 4 * DSL, RING = DQ_RING;
+      // fragment j: K (j even) or V (j odd), row block (j/2)/DSL, slice (j/2)%DSL
+      const auto frag = [&](int j) {
+        const bf16* tile = (j & 1) ? v_lds[idx] : k_lds[idx];
+        return ld8_swz<D>(tile, ((j / 2) / DSL) * 32 + lo, ((j / 2) % DSL) * 32 + hi * 16);
+      };
+      short8 f[RING];
 #pragma unroll
-      for (int ds = 0; ds < DSL; ++ds) {
-        const short8 kf = ld8_swz<D>(k_lds[idx], t * 32 + lo, ds * 32 + hi * 16);
-        const short8 vf = ld8_swz<D>(v_lds[idx], t * 32 + lo, ds * 32 + hi * 16);
-        st[t] = mfma32(kf, qf[ds], st[t]);
-        dpt[t] = mfma32(vf, dof[ds], dpt[t]);
+      for (int j = 0; j < RING; ++j) f[j] = frag(j);
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int t = (j / 2) / DSL, ds = (j / 2) % DSL;
+        if (j & 1) dpt[t] = mfma32(f[j % RING], dof[ds], dpt[t]);
+        else st[t] = mfma32(f[j % RING], qf[ds], st[t]);
+        if (j + RING < NF) f[j % RING] = frag(j + RING);
+      }
+      if (!DOC) {
+        __builtin_amdgcn_sched_group_barrier(0x100, RING, 0);
+#pragma unroll
+        for (int j = 0; j < NF - RING; ++j) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, RING, 0);
       }
     }
     // ---- causal mask, on the wave's diagonal tile only (wave-uniform; no
@@ -976,7 +1092,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
 //
 // Two shapes are instantiated: NW=8, DBUF=2 for S % 128 == 0 — one stage
 // feeds 128 k-rows, double-buffered with prefetch-behind-barrier (one
-// barrier per q-tile) — and NW=4, DBUF=1 for the other S % 64 == 0.
+// barrier per q-tile, untracked stage loads and one vmcnt(0) in front of
+// it) — and NW=4, DBUF=1 for the other S % 64 == 0.
 // direct=1: the block runs every q-tile of its k-tile and stores bf16
 // dK/dV itself — no reduce kernel, no per-split partials. Causal blocks
 // take k-tile kt and then n_kt-1-kt (their trip counts always add up to
@@ -1090,22 +1207,55 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     const bf16* dOb_ = dO + ((int64_t)b * S * H + h_) * D;
     const bf16* Qtb_ = Qt + ((int64_t)(b * H + h_) * D) * S;
     const bf16* dOtb_ = dOt + ((int64_t)(b * H + h_) * D) * S;
-    stage_tile<64, D, NW * 64>(Qb_ + (int64_t)q0g_ * sqs, sqs, q_lds[buf], threadIdx.x);
-    stage_tile<64, D, NW * 64>(dOb_ + (int64_t)q0g_ * H * D, (int64_t)H * D, do_lds[buf], threadIdx.x);
-    stage_tile<D, 64, NW * 64>(Qtb_ + q0g_, S, qt_lds[buf], threadIdx.x);
-    stage_tile<D, 64, NW * 64>(dOtb_ + q0g_, S, dot_lds[buf], threadIdx.x);
+    // DBUF == 2: untracked loads, waited for at the tile boundary only
+    constexpr bool UT = DBUF == 2;
+    stage_tile<64, D, NW * 64, UT>(Qb_ + (int64_t)q0g_ * sqs, sqs, q_lds[buf], threadIdx.x);
+    stage_tile<64, D, NW * 64, UT>(dOb_ + (int64_t)q0g_ * H * D, (int64_t)H * D, do_lds[buf], threadIdx.x);
+    stage_tile<D, 64, NW * 64, UT>(Qtb_ + q0g_, S, qt_lds[buf], threadIdx.x);
+    stage_tile<D, 64, NW * 64, UT>(dOtb_ + q0g_, S, dot_lds[buf], threadIdx.x);
   };
-  if (DBUF == 2 && n_iter > 0) stage_it(0, 0);
+  // DBUF == 2: the lse/delta of q-tile it+1 (this lane's query of each 16-
+  // row sub) are loaded one tile ahead, issued in front of that tile's
+  // stage and waited for with it at the tile boundary, so no wait for
+  // them stands behind the LDS-DMA (vmcnt retires in order: waiting for a
+  // load issued after the stage would wait for the whole stage).
+  float lse_nx[4], dl_nx[4], lse_c[4], dl_c[4];
+  const auto load_rowc = [&](int it) {
+    const int g_ = it / tiles_per_g;
+    const int q0g_ = q_start + (it - g_ * tiles_per_g) * 64 * splits;
+    const int64_t o_ = (int64_t)(hkv * group + g_) * S + q0g_ + li;
+#pragma unroll
+    for (int sub = 0; sub < 4; ++sub) {
+      lse_nx[sub] = lse_t[o_ + sub * 16];
+      dl_nx[sub] = dl_t[o_ + sub * 16];
+    }
+  };
+  if (DBUF == 2 && n_iter > 0) {
+    load_rowc(0);
+    stage_it(0, 0);
+  }
   for (int it = 0; it < n_iter; ++it) {
     const int g = it / tiles_per_g;
     const int q0g = q_start + (it - g * tiles_per_g) * 64 * splits;
     const int cur = (DBUF == 2) ? (it & 1) : 0;
     {
+      // DBUF == 2, tile boundary on every path (the skip below included):
+      // this wave's share of tile `it` has landed, then the barrier
+      if (DBUF == 2) stage_wait_all();
       __syncthreads();
       if (DBUF == 2) {
-        // prefetch-behind-barrier: next tile's loads land under this
-        // tile's compute; the next barrier drains them
-        if (it + 1 < n_iter) stage_it(it + 1, cur ^ 1);
+        // prefetch-behind-barrier: the next tile's untracked loads land
+        // under this tile's compute; nothing waits for them before the
+        // next tile boundary
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) {
+          lse_c[sub] = lse_nx[sub];
+          dl_c[sub] = dl_nx[sub];
+        }
+        if (it + 1 < n_iter) {
+          load_rowc(it + 1);
+          stage_it(it + 1, cur ^ 1);
+        }
       } else {
         stage_it(it, 0);
         __syncthreads();
@@ -1127,8 +1277,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
         }
         const int qg = q0g + sub * 16 + li;
         const int64_t o = (int64_t)(hkv * group + g) * S + qg;
-        const float lse_q = lse_t[o];
-        const float dl_q = dl_t[o];
+        const float lse_q = (DBUF == 2) ? lse_c[sub] : lse_t[o];
+        const float dl_q = (DBUF == 2) ? dl_c[sub] : dl_t[o];
         float pv[4], dsv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
