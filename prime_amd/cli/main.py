@@ -716,6 +716,10 @@ def generate_cmd(
     kv_dtype: str = typer.Option("bf16", "--kv-dtype", callback=_kv_dtype_option,
                                  help=_KV_DTYPE_HELP + "; with fp8 a single "
                                  "prompt runs as a ragged batch of one"),
+    lookahead: int = typer.Option(0, "--lookahead", min=0, max=7, help=(
+        "prompt-lookup speculative decoding: draft this many tokens per step "
+        "and verify them in one multi-token decode pass (greedy sequences, "
+        "bf16 cache; runs as a ragged batch)")),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch
@@ -754,14 +758,16 @@ def generate_cmd(
     else:
         groups = [g for pt in prompt_tokens for g in pt.split(";") if g.strip()]
         prompts = [[int(t) for t in g.split(",")] for g in groups]
-    if len(prompts) > 1 or kv_dtype != "bf16":
+    if len(prompts) > 1 or kv_dtype != "bf16" or lookahead:
         # several prompts of different lengths: one ragged batch, one output
-        # line (prompt + new tokens) per prompt; the fp8 cache exists on the
-        # ragged path only, so it takes a single prompt this way too
+        # line (prompt + new tokens) per prompt; the fp8 cache and lookahead
+        # decoding exist on the ragged path only, so they take a single
+        # prompt this way too
         from ..models.generate import generate_batch
 
         outs = generate_batch(m, prompts, max_new, temperature=temperature,
-                              top_k=top_k, seed=seed, kv_dtype=kv_dtype)
+                              top_k=top_k, seed=seed, kv_dtype=kv_dtype,
+                              lookahead=lookahead)
         for p_ids, new in zip(prompts, outs):
             if tok is not None:
                 from ..utils.tokenizer import decode as tok_decode

@@ -180,6 +180,7 @@ def generate_batch(
     stop_token_ids=None,
     use_graph: bool = True,
     kv_dtype: str = "bf16",
+    lookahead: int = 0,
 ) -> list[list[int]]:
     """Ragged batched generation: `prompts` is a list of token-id lists of
     different lengths; returns the NEW tokens of each. max_new_tokens,
@@ -202,7 +203,22 @@ def generate_batch(
     e4m3 bytes with one fp32 scale per (row, kv head) (ops.KVCacheFp8): half
     the memory and traffic. The prefill attends to the unquantised k and v,
     so the first new token is that of the bf16 cache; later tokens see the
-    quantised rows."""
+    quantised rows.
+
+    lookahead = K > 0 (at most 7, bf16 cache) turns on prompt-lookup drafting
+    for the greedy sequences: the draft is the K tokens that followed the
+    most recent earlier occurrence of the sequence's last two tokens, and one
+    multi-token decode step (T = K + 1 rows per sequence) verifies it,
+    keeping the longest prefix the model agrees with plus one corrected
+    token. Rejected rows are overwritten by the next step. Sampling
+    sequences take one token per step in the same batch. The host writes
+    the step's tokens, positions and row counts; the graph is captured once
+    per (batch bucket, cache-length bucket, device, T)."""
+    lookahead = int(lookahead)
+    if not 0 <= lookahead <= 7:
+        raise ValueError(f"lookahead must be in 0..7 (got {lookahead})")
+    if lookahead and kv_dtype != "bf16":
+        raise NotImplementedError("lookahead decoding reads a bf16 KV cache")
     if kv_dtype not in KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got "
                          f"{kv_dtype!r})")
@@ -241,7 +257,8 @@ def generate_batch(
     sessions = getattr(model, "_decode_sessions", None)
     if sessions is None:
         sessions = model._decode_sessions = {}
-    key = ("ragged", Bk, smax, dev.index, kv_dtype)
+    key = ("ragged", Bk, smax, dev.index, kv_dtype) if not lookahead \
+        else ("ragged_multi", Bk, smax, dev.index, lookahead + 1)
     sess = sessions.get(key) if graphing else None
     if sess is None:
         if kv_dtype == "fp8":
@@ -256,10 +273,15 @@ def generate_batch(
                 for _ in range(cfg.n_layers)
             ]
         sess = _ragged_state(caches, Bk, dev)
+        if lookahead:
+            sess["tok"] = torch.zeros(Bk, lookahead + 1, dtype=torch.int64,
+                                      device=dev)
+            sess["n_new"] = torch.ones(Bk, dtype=torch.int32, device=dev)
         if graphing:
             # capture BEFORE prefill, as _build_session does: the warmup and
             # capture passes write junk rows that the prefill overwrites
-            _capture_ragged(model, sess)
+            _capture_ragged(model, sess, _multi_step if lookahead
+                            else _ragged_step)
             sessions[key] = sess
     caches = sess["caches"]
     gens = []
@@ -301,6 +323,11 @@ def generate_batch(
     logits = model.lm_head(h[torch.arange(n, device=dev), last])
     live = [b for b in range(n) if not done[b]]
     accept(pick(logits, live))
+
+    if lookahead:
+        _decode_lookahead(model, sess, graphing, lookahead, prompts, out, done,
+                          max_new, stops, temps, topks, gens)
+        return out
 
     # ---- ragged decode: slot b sits at pos[b]; finished / padding = idle
     def write_state():
@@ -354,19 +381,87 @@ def _ragged_step(model, sess):
     return logits
 
 
-def _capture_ragged(model, sess):
-    """Capture _ragged_step as one replayable hipGraph (warm-up on a side
+def _capture_ragged(model, sess, step=_ragged_step):
+    """Capture `step` as one replayable hipGraph (warm-up on a side
     stream, per the torch CUDA-graphs contract, as _build_session)."""
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
         for _ in range(2):
-            _ragged_step(model, sess)
+            step(model, sess)
     torch.cuda.current_stream().wait_stream(s)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        sess["logits"] = _ragged_step(model, sess)
+        sess["logits"] = step(model, sess)
     sess["graph"] = graph
+
+
+def _multi_step(model, sess):
+    """Up to T tokens for every live slot: logits [Bk, T, vocab]. The host
+    writes tok / pos / lens / n_new before every step."""
+    h = model(sess["tok"], caches=sess["caches"], seq_pos=sess)
+    return model.lm_head(h)
+
+
+def _prompt_lookup(seq, k: int) -> list:
+    """The (at most k) tokens that followed the most recent earlier
+    occurrence of seq's last two tokens; [] without one."""
+    if len(seq) < 3:
+        return []
+    a, b = seq[-2], seq[-1]
+    for i in range(len(seq) - 3, -1, -1):
+        if seq[i] == a and seq[i + 1] == b:
+            return seq[i + 2:i + 2 + k]
+    return []
+
+
+def _decode_lookahead(model, sess, graphing, K, prompts, out, done, max_new,
+                      stops, temps, topks, gens):
+    """Decode loop of generate_batch(lookahead=K): each step feeds a live
+    sequence its last token plus a prompt-lookup draft (greedy sequences
+    only, never longer than the tokens it may still produce) and accepts
+    token by token while the model's argmax agrees with the draft."""
+    n, Bk, T = len(prompts), sess["tok"].shape[0], K + 1
+    while not all(done):
+        live = [b for b in range(n) if not done[b]]
+        tok = torch.zeros(Bk, T, dtype=torch.int64)
+        pos = torch.full((Bk,), -1, dtype=torch.int32)
+        nn = torch.zeros(Bk, dtype=torch.int32)
+        drafts = {}
+        for b in live:
+            d = []
+            if temps[b] <= 0:
+                d = _prompt_lookup(prompts[b] + out[b], K)
+                d = d[:max_new[b] - len(out[b]) - 1]
+            drafts[b] = d
+            row = [out[b][-1]] + d
+            tok[b, :len(row)] = torch.tensor(row, dtype=torch.int64)
+            pos[b] = len(prompts[b]) + len(out[b]) - 1
+            nn[b] = len(row)
+        sess["tok"].copy_(tok)
+        sess["pos"].copy_(pos)
+        sess["lens"].copy_((pos + 1) * (nn > 0))
+        sess["n_new"].copy_(nn)
+        if graphing:
+            sess["graph"].replay()
+            logits = sess["logits"]
+        else:
+            logits = _multi_step(model, sess)
+        greedy = None
+        for b in live:
+            if temps[b] > 0:
+                ys = [int(_sample(logits[b, :1], temps[b], topks[b], gens[b]))]
+            else:
+                if greedy is None:  # one device sync for all greedy rows
+                    greedy = logits.argmax(-1).tolist()
+                ys = greedy[b][:len(drafts[b]) + 1]
+            for t, y in enumerate(ys):
+                out[b].append(y)
+                if len(out[b]) >= max_new[b] or y in stops:
+                    done[b] = True
+                    break
+                if t >= len(drafts[b]) or drafts[b][t] != y:
+                    break
 
 
 def _sample(logits: torch.Tensor, temperature: float, top_k: int, gen) -> torch.Tensor:

@@ -60,6 +60,26 @@ class Attention(nn.Module):
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
+        if seq_pos is not None and "n_new" in seq_pos:
+            # multi-token ragged decode (speculative verification): up to S
+            # new tokens per sequence, seq_pos["n_new"] of them live
+            if cache is None:
+                raise ValueError("seq_pos needs KV caches")
+            if doc_start is not None or pos_dev is not None \
+                    or self.sp_group is not None:
+                raise ValueError("seq_pos cannot be combined with doc_start, "
+                                 "pos_dev or sequence parallelism")
+            if isinstance(cache, ops.KVCacheFp8):
+                raise NotImplementedError(
+                    "multi-token decode (seq_pos with n_new) reads a bf16 KV "
+                    "cache; an fp8 variant does not exist yet")
+            kc, vc = cache
+            q = ops.decode_qkv_append_multi(
+                self.wqkv(x), cos, sin, kc, vc, seq_pos["pos"],
+                seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)
+            o = ops.attn_decode_ragged_multi(q, kc, vc, seq_pos["lens"],
+                                             seq_pos["n_new"])
+            return self.wo(o.reshape(B, S, cfg.n_heads * hd))
         if seq_pos is not None:
             # ragged batched decode: one new token per sequence, each at its
             # own position (seq_pos["pos"]) and cache length (seq_pos["lens"])
@@ -235,7 +255,11 @@ class Llama(nn.Module):
         seq_pos: ragged batched decode, a dict of int32 [B] device tensors
         {"pos": position of each sequence's new token (negative = idle slot),
         "lens": rows it attends to, pos + 1 (0 = idle slot)}; needs S == 1
-        and caches.
+        and caches. A third key "n_new" (live new tokens per sequence)
+        selects the multi-token kernels: tokens may then be [B,T] with T up
+        to 8, token t of sequence b sits at pos[b] + t and attends to
+        lens[b] + t rows, and rows t >= n_new[b] of the result are junk-free
+        but meaningless (their attention output is zero).
         doc_start: optional int32 [B,S] document mask (ops.doc_starts) for
         packed sequences, shared by every layer. Positions are NOT reset per
         document: RoPE is relative, so attention within a document does not
@@ -244,7 +268,7 @@ class Llama(nn.Module):
             raise ValueError("doc_start cannot be combined with KV caches or "
                              "decode positions")
         if seq_pos is not None:
-            if tokens.shape[1] != 1 or not caches:
+            if (tokens.shape[1] != 1 and "n_new" not in seq_pos) or not caches:
                 raise ValueError("seq_pos needs one token per sequence "
                                  "(S == 1) and KV caches")
             if doc_start is not None or pos_dev is not None \

@@ -9,12 +9,17 @@ from __future__ import annotations
 
 import os
 import subprocess
+import tempfile
 from pathlib import Path
 
 OPS_DIR = Path(__file__).resolve().parent
 CSRC = OPS_DIR / "csrc"
 LIB_PATH = OPS_DIR / "libprime_hip.so"
 ARCH = os.environ.get("PRIME_AMD_ARCH", "gfx950")
+# sources compiled on their own, without the packed fp32 VALU instructions
+# (v_pk_add/mul/fma_f32); new kernel files go here
+NO_PACKED_FP32 = ("decode_multi.hip",)
+_NO_PACKED_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def sources() -> list[Path]:
@@ -50,21 +55,31 @@ def build(force: bool = False, verbose: bool = True) -> Path:
     srcs = sources()
     if not srcs:
         raise RuntimeError(f"no .hip sources under {CSRC}")
-    cmd = [
-        "hipcc",
-        f"--offload-arch={ARCH}",
-        "-O3",
-        "-std=c++17",
-        "-shared",
-        "-fPIC",
-        "-fvisibility=hidden",
-        *[str(s) for s in srcs],
-        "-o",
-        str(LIB_PATH),
-    ]
-    if verbose:
-        print(f"[prime_amd] building {LIB_PATH.name}: {' '.join(cmd)}", flush=True)
-    subprocess.run(cmd, check=True, cwd=str(CSRC))
+    base = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
+            "-fvisibility=hidden"]
+    with tempfile.TemporaryDirectory(prefix="prime_hip_") as tmp:
+        objs = []
+        for s in srcs:
+            if s.name in NO_PACKED_FP32:
+                obj = str(Path(tmp) / (s.stem + ".o"))
+                cmd = [*base, *_NO_PACKED_FLAGS, "-c", str(s), "-o", obj]
+                if verbose:
+                    print(f"[prime_amd] compiling {s.name}: {' '.join(cmd)}",
+                          flush=True)
+                subprocess.run(cmd, check=True, cwd=str(CSRC))
+                objs.append(obj)
+        cmd = [
+            *base,
+            "-shared",
+            *objs,  # before the sources: hipcc reads what follows one as HIP
+            *[str(s) for s in srcs if s.name not in NO_PACKED_FP32],
+            "-o",
+            str(LIB_PATH),
+        ]
+        if verbose:
+            print(f"[prime_amd] building {LIB_PATH.name}: {' '.join(cmd)}",
+                  flush=True)
+        subprocess.run(cmd, check=True, cwd=str(CSRC))
     LIB_PATH.with_suffix(".so.hash").write_text(source_hash() + "\n")
     return LIB_PATH
 

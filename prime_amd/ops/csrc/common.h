@@ -97,4 +97,10 @@ static inline int prime_grid(int64_t work_items, int block) {
   return (int)g;
 }
 
+// Builds one kernel without the packed fp32 VALU instructions
+// (v_pk_add/mul/fma_f32) when it shares a file with kernels that keep them.
+// Only for kernels whose callees are all force-inlined; a whole file goes
+// into NO_PACKED_FP32 of ops/build.py instead.
+#define PRIME_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
 #define PRIME_API extern "C" __attribute__((visibility("default")))

@@ -11,6 +11,12 @@
 // q and k are bit-identical to prime_rope at pos_offset = pos[b].
 // A slot with pos[b] < 0 or pos[b] >= min(Smax, T) is idle: no cache row is
 // written for it and its q rows are zeros.
+//
+// decode_qkv_append_multi_kernel is the same pass for up to TN new tokens per
+// sequence (qkv [B,TN,(H+2Hkv)*D], qout [B,TN,H,D]): token t of slot b is
+// rotated at pos[b] + t and stored to cache row pos[b] + t. It is dead, with
+// no cache row written and zero q rows, if pos[b] < 0, t >= n_new[b] or
+// pos[b] + t >= min(Smax, T).
 #include "common.h"
 
 __global__ void decode_qkv_append_kernel(
@@ -88,5 +94,88 @@ PRIME_API int prime_decode_qkv_append(hipStream_t stream, const void* qkv,
                      (bf16*)vc, (const float*)cos_t, (const float*)sin_t,
                      (const int*)pos, nrows, (int)H, (int)Hkv, (int)D,
                      (int)Smax, (int)T, 1.f);
+  return (int)hipGetLastError();
+}
+
+PRIME_NO_PK_F32 __global__ void decode_qkv_append_multi_kernel(
+    const bf16* __restrict__ qkv, bf16* __restrict__ qout,
+    bf16* __restrict__ kc, bf16* __restrict__ vc,
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+    const int* __restrict__ pos, const int* __restrict__ n_new, int64_t nrows,
+    int TN, int H, int Hkv, int D, int Smax, int T, float sign) {
+  const int half = D / 2;
+  const int hv = half / 4;
+  const int NH = H + 2 * Hkv;
+  const int lim = min(Smax, T);
+  const int64_t total = nrows * hv;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = idx / hv;  // (b, t, head of the packed row)
+    const int i4 = (int)(idx - row * hv) * 4;
+    const int64_t bt = row / NH;
+    const int hh = (int)(row - bt * NH);
+    const int64_t b = bt / TN;
+    const int t = (int)(bt - b * TN);
+    const int p0 = pos[b];
+    // p0 < lim - t, not p0 + t < lim: no overflow for any p0
+    const bool live = p0 >= 0 && t < n_new[b] && p0 < lim - t;
+    const int p = p0 + t;
+    bf16* dst;
+    bool rot = true;
+    if (hh < H) {
+      dst = qout + (bt * H + hh) * D;
+      if (!live) {
+        bf16x4 z;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z.v[j] = f2bf(0.f);
+        *reinterpret_cast<bf16x4*>(dst + i4) = z;
+        *reinterpret_cast<bf16x4*>(dst + half + i4) = z;
+        continue;
+      }
+    } else {
+      if (!live) continue;
+      const int hk = hh - H;
+      if (hk < Hkv) {
+        dst = kc + ((b * Smax + p) * Hkv + hk) * D;
+      } else {
+        dst = vc + ((b * Smax + p) * Hkv + (hk - Hkv)) * D;
+        rot = false;
+      }
+    }
+    const bf16* xr = qkv + row * D;
+    const bf16x4 x1 = *reinterpret_cast<const bf16x4*>(xr + i4);
+    const bf16x4 x2 = *reinterpret_cast<const bf16x4*>(xr + half + i4);
+    bf16x4 y1 = x1, y2 = x2;
+    if (rot) {
+      const f32x4v c =
+          *reinterpret_cast<const f32x4v*>(cos_t + (int64_t)p * half + i4);
+      const f32x4v sn =
+          *reinterpret_cast<const f32x4v*>(sin_t + (int64_t)p * half + i4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        rope_rot(x1.v[j], x2.v[j], c.v[j], sn.v[j], sign, y1.v[j], y2.v[j]);
+    }
+    *reinterpret_cast<bf16x4*>(dst + i4) = y1;
+    *reinterpret_cast<bf16x4*>(dst + half + i4) = y2;
+  }
+}
+
+// TN: new tokens per sequence in qkv; T: rows of the cos / sin tables.
+PRIME_API int prime_decode_qkv_append_multi(
+    hipStream_t stream, const void* qkv, void* qout, void* kc, void* vc,
+    const void* cos_t, const void* sin_t, const void* pos, const void* n_new,
+    int64_t B, int64_t TN, int64_t H, int64_t Hkv, int64_t D, int64_t Smax,
+    int64_t T) {
+  if ((D != 64 && D != 128) || B < 1 || TN < 1 || TN > 8 || H < 1 ||
+      Hkv < 1 || Smax < 1 || T < 1 || Smax > 0x7fffffff || T > 0x7fffffff ||
+      !pos || !n_new)
+    return hipErrorInvalidValue;
+  const int64_t nrows = B * TN * (H + 2 * Hkv);
+  const int grid = prime_grid(nrows * (D / 8), 256);
+  hipLaunchKernelGGL(decode_qkv_append_multi_kernel, dim3(grid), dim3(256), 0,
+                     stream, (const bf16*)qkv, (bf16*)qout, (bf16*)kc,
+                     (bf16*)vc, (const float*)cos_t, (const float*)sin_t,
+                     (const int*)pos, (const int*)n_new, nrows, (int)TN,
+                     (int)H, (int)Hkv, (int)D, (int)Smax, (int)T, 1.f);
   return (int)hipGetLastError();
 }

@@ -1300,6 +1300,145 @@ def decode_qkv_append(qkv, cos, sin, k_cache, v_cache, pos, n_heads: int,
     return q
 
 
+# --------------------------------------- multi-token ragged decode (MFMA)
+# Keys per workgroup step of attn_decode_ragged_multi (4 waves x 32 keys);
+# split_rows is a multiple of it. decode_ragged_split's results are.
+DECODE_MULTI_CHUNK = 128
+_MULTI_MAX_T = 8
+_MULTI_MAX_ROWS = 64
+_MULTI_WS: dict = {}  # (B, Hkv, T*G, D, nsplit, device) -> fp32 partials
+
+
+def _multi_live(L: int, n: int, T: int, Smax: int):
+    """Clamped (L0, n) of one slot, as the kernels compute them."""
+    L0 = min(max(L, 0), Smax)
+    if L0 == 0:
+        return 0, 0
+    return L0, min(max(n, 0), min(T, Smax - L0 + 1))
+
+
+def _reject_fp8(cache, op: str) -> None:
+    if isinstance(cache, KVCacheFp8):
+        raise NotImplementedError(f"{op} reads a bf16 KV cache; an fp8 "
+                                  f"(KVCacheFp8) variant does not exist yet")
+
+
+def attn_decode_ragged_multi(q, k_cache, v_cache, lens, n_new,
+                             split_rows=None) -> torch.Tensor:
+    """Decode attention for up to T new tokens per sequence (speculative /
+    multi-token verification): q [B,T,H,D] against caches [B,Smax,Hkv,D] that
+    already hold the new tokens' rows. `lens` (int32 [B]) is the number of
+    rows the FIRST new token attends to, `n_new` (int32 [B]) the live new
+    tokens; both are read at kernel time. With L0 = clamp(lens[b], 0, Smax)
+    and n = clamp(n_new[b], 0, min(T, Smax - L0 + 1)) (n = 0 if L0 == 0),
+    query t < n attends to rows [0, L0 + t) and query t >= n gives exact
+    zeros; no row at or beyond L0 + n - 1 is read. Returns [B,T,H,D].
+    Supported: D in {64, 128}, G = H/Hkv in {1, 2, 4, 8}, T <= 8, T*G <= 64.
+    `split_rows` overrides decode_ragged_split (a multiple of
+    DECODE_MULTI_CHUNK)."""
+    _reject_fp8(k_cache, "attn_decode_ragged_multi")
+    if q.dim() != 4:
+        raise ValueError("attn_decode_ragged_multi needs q [B,T,H,D]")
+    B, T, H, D = q.shape
+    _, Smax, Hkv, _ = k_cache.shape
+    for name, v in (("lens", lens), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        o = torch.zeros_like(q)
+        for b, (L, n) in enumerate(zip(lens.tolist(), n_new.tolist())):
+            L0, n = _multi_live(L, n, T, Smax)
+            for t in range(n):
+                o[b, t] = ref.attention(
+                    q[b:b + 1, t:t + 1], k_cache[b:b + 1, :L0 + t],
+                    v_cache[b:b + 1, :L0 + t], causal=False)[0, 0]
+        return o
+    G = H // Hkv if H % Hkv == 0 else 0
+    if D not in (64, 128) or G not in _RAGGED_GROUPS \
+            or not 1 <= T <= _MULTI_MAX_T or T * G > _MULTI_MAX_ROWS:
+        raise NotImplementedError(
+            f"attn_decode_ragged_multi needs head_dim in {{64, 128}}, a GQA "
+            f"group size in {_RAGGED_GROUPS}, 1 <= T <= {_MULTI_MAX_T} and "
+            f"T * group <= {_MULTI_MAX_ROWS} (got head_dim={D}, heads={H}, "
+            f"kv_heads={Hkv}, T={T})")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attn_decode_ragged_multi needs contiguous KV caches")
+    if split_rows is None:
+        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % DECODE_MULTI_CHUNK != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{DECODE_MULTI_CHUNK} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    # one workspace per shape, reused: a captured graph sees stable pointers
+    key = (B, Hkv, T * G, D, nsplit, q.device.index)
+    ws = _MULTI_WS.get(key)
+    if ws is None:
+        ws = _MULTI_WS[key] = torch.empty(
+            B * Hkv, nsplit, T * G * (D + 2), device=q.device,
+            dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_decode_ragged_multi(
+            stream_of(q), ptr(q), ptr(k_cache), ptr(v_cache), ptr(o), ptr(ws),
+            ptr(lens), ptr(n_new), B, T, H, Hkv, Smax, D, split_rows, D**-0.5,
+        ),
+        "attn_decode_ragged_multi",
+    )
+    return o
+
+
+def decode_qkv_append_multi(qkv, cos, sin, k_cache, v_cache, pos, n_new,
+                            n_heads: int, n_kv_heads: int) -> torch.Tensor:
+    """decode_qkv_append for up to T new tokens per sequence: qkv
+    [B,T,(H+2Hkv)*D]; token t of slot b is rotated at pos[b] + t (bit-identical
+    to apply_rope(..., pos_offset=pos[b] + t)), its k and v go to cache row
+    pos[b] + t, and the rotated q is returned as [B,T,H,D]. `pos` and `n_new`
+    are int32 [B] device tensors. A token is dead if pos[b] < 0, t >=
+    n_new[b] or pos[b] + t >= min(Smax, len(cos)): it writes no cache row and
+    its q rows are zeros."""
+    _reject_fp8(k_cache, "decode_qkv_append_multi")
+    H, Hkv = n_heads, n_kv_heads
+    _, Smax, Hkv_c, D = k_cache.shape
+    R = cos.shape[0]
+    if qkv.dim() != 3 or qkv.shape[2] != (H + 2 * Hkv) * D or Hkv_c != Hkv:
+        raise ValueError(f"decode_qkv_append_multi: qkv {tuple(qkv.shape)} does "
+                         f"not match heads={H}, kv_heads={Hkv}, head_dim={D}")
+    B, T = qkv.shape[:2]
+    for name, v in (("pos", pos), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != qkv.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on qkv's device")
+    if not _is_hip(qkv):
+        q = torch.zeros(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+        x = qkv.view(B, T, H + 2 * Hkv, D)
+        for b, (p0, n) in enumerate(zip(pos.tolist(), n_new.tolist())):
+            for t in range(T):
+                p = p0 + t
+                if p0 < 0 or t >= n or p >= min(Smax, R):
+                    continue
+                xt = x[b:b + 1, t:t + 1]
+                q[b, t] = ref.apply_rope(xt[:, :, :H], cos, sin, p)[0, 0]
+                k_cache[b, p] = ref.apply_rope(xt[:, :, H:H + Hkv], cos, sin, p)[0, 0]
+                v_cache[b, p] = x[b, t, H + Hkv:]
+        return q
+    if D not in (64, 128) or not 1 <= T <= _MULTI_MAX_T:
+        raise NotImplementedError(
+            f"decode_qkv_append_multi needs head_dim in {{64, 128}} and "
+            f"1 <= T <= {_MULTI_MAX_T} (got head_dim={D}, T={T})")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("decode_qkv_append_multi needs contiguous KV caches")
+    qkv = qkv.contiguous()
+    q = torch.empty(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_decode_qkv_append_multi(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(k_cache), ptr(v_cache),
+            ptr(cos), ptr(sin), ptr(pos), ptr(n_new), B, T, H, Hkv, D, Smax, R,
+        ),
+        "decode_qkv_append_multi",
+    )
+    return q
+
+
 # ------------------------------------------------------------ fp8 KV cache
 class KVCacheFp8(NamedTuple):
     """One layer's fp8 KV cache. k, v: float8_e4m3fn [B,Smax,Hkv,D];
