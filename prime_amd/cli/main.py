@@ -719,7 +719,7 @@ def generate_cmd(
     lookahead: int = typer.Option(0, "--lookahead", min=0, max=7, help=(
         "prompt-lookup speculative decoding: draft this many tokens per step "
         "and verify them in one multi-token decode pass (greedy sequences, "
-        "bf16 cache; runs as a ragged batch)")),
+        "bf16 or fp8 cache; runs as a ragged batch)")),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch

@@ -205,7 +205,7 @@ def generate_batch(
     so the first new token is that of the bf16 cache; later tokens see the
     quantised rows.
 
-    lookahead = K > 0 (at most 7, bf16 cache) turns on prompt-lookup drafting
+    lookahead = K > 0 (at most 7, either cache type) turns on prompt-lookup drafting
     for the greedy sequences: the draft is the K tokens that followed the
     most recent earlier occurrence of the sequence's last two tokens, and one
     multi-token decode step (T = K + 1 rows per sequence) verifies it,
@@ -213,12 +213,11 @@ def generate_batch(
     token. Rejected rows are overwritten by the next step. Sampling
     sequences take one token per step in the same batch. The host writes
     the step's tokens, positions and row counts; the graph is captured once
-    per (batch bucket, cache-length bucket, device, T)."""
+    per (batch bucket, cache-length bucket, device, T, kv_dtype). With an fp8
+    cache it needs a model on the GPU."""
     lookahead = int(lookahead)
     if not 0 <= lookahead <= 7:
         raise ValueError(f"lookahead must be in 0..7 (got {lookahead})")
-    if lookahead and kv_dtype != "bf16":
-        raise NotImplementedError("lookahead decoding reads a bf16 KV cache")
     if kv_dtype not in KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got "
                          f"{kv_dtype!r})")
@@ -226,6 +225,10 @@ def generate_batch(
     cfg = model.cfg
     p0 = next(model.parameters())
     dev, dtype = p0.device, p0.dtype
+    if lookahead and kv_dtype != "bf16" and dev.type != "cuda":
+        # the model's guard (Attention.forward), raised before any work
+        raise NotImplementedError("lookahead decoding over an fp8 KV cache "
+                                  "runs on the GPU only")
     n = len(prompts)
     if n == 0:
         return []
@@ -258,7 +261,7 @@ def generate_batch(
     if sessions is None:
         sessions = model._decode_sessions = {}
     key = ("ragged", Bk, smax, dev.index, kv_dtype) if not lookahead \
-        else ("ragged_multi", Bk, smax, dev.index, lookahead + 1)
+        else ("ragged_multi", Bk, smax, dev.index, lookahead + 1, kv_dtype)
     sess = sessions.get(key) if graphing else None
     if sess is None:
         if kv_dtype == "fp8":

@@ -70,9 +70,17 @@ class Attention(nn.Module):
                 raise ValueError("seq_pos cannot be combined with doc_start, "
                                  "pos_dev or sequence parallelism")
             if isinstance(cache, ops.KVCacheFp8):
-                raise NotImplementedError(
-                    "multi-token decode (seq_pos with n_new) reads a bf16 KV "
-                    "cache; an fp8 variant does not exist yet")
+                # pinned by test_decode_multi_cpu.py::test_model_guards
+                if not cache.k.is_cuda:
+                    raise NotImplementedError(
+                        "multi-token decode (seq_pos with n_new) over an fp8 "
+                        "KV cache runs on the GPU only")
+                q = ops.decode_qkv_append_multi_fp8(
+                    self.wqkv(x), cos, sin, cache, seq_pos["pos"],
+                    seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)
+                o = ops.attn_decode_ragged_multi_fp8(
+                    q, cache, seq_pos["lens"], seq_pos["n_new"])
+                return self.wo(o.reshape(B, S, cfg.n_heads * hd))
             kc, vc = cache
             q = ops.decode_qkv_append_multi(
                 self.wqkv(x), cos, sin, kc, vc, seq_pos["pos"],

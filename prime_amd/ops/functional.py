@@ -1633,6 +1633,119 @@ def attn_decode_ragged_fp8(q, cache: KVCacheFp8, lens, split_rows=None) -> torch
     return o
 
 
+def attn_decode_ragged_multi_fp8(q, cache: KVCacheFp8, lens, n_new,
+                                 split_rows=None) -> torch.Tensor:
+    """attn_decode_ragged_multi over an fp8 cache: q [B,T,H,D], the same
+    lens / n_new clamp, dead-query, supported-shape and split_rows rules; the
+    values attended to are kv_cache_dequant(cache). No row and no scale at
+    or beyond L0 + n - 1 is read."""
+    _check_fp8_cache(cache, "attn_decode_ragged_multi_fp8")
+    if q.dim() != 4:
+        raise ValueError("attn_decode_ragged_multi_fp8 needs q [B,T,H,D]")
+    B, T, H, D = q.shape
+    _, Smax, Hkv, _ = cache.k.shape
+    for name, v in (("lens", lens), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        o = torch.zeros_like(q)
+        for b, (L, n) in enumerate(zip(lens.tolist(), n_new.tolist())):
+            L0, n = _multi_live(L, n, T, Smax)
+            if n == 0:
+                continue
+            kf, vf = kv_cache_dequant(KVCacheFp8(
+                *(t[b:b + 1, :L0 + n - 1] for t in cache)))
+            for t in range(n):
+                o[b, t] = ref.attention(q[b:b + 1, t:t + 1], kf[:, :L0 + t],
+                                        vf[:, :L0 + t], causal=False)[0, 0]
+        return o
+    G = H // Hkv if H % Hkv == 0 else 0
+    if D not in (64, 128) or G not in _RAGGED_GROUPS \
+            or not 1 <= T <= _MULTI_MAX_T or T * G > _MULTI_MAX_ROWS:
+        raise NotImplementedError(
+            f"attn_decode_ragged_multi_fp8 needs head_dim in {{64, 128}}, a GQA "
+            f"group size in {_RAGGED_GROUPS}, 1 <= T <= {_MULTI_MAX_T} and "
+            f"T * group <= {_MULTI_MAX_ROWS} (got head_dim={D}, heads={H}, "
+            f"kv_heads={Hkv}, T={T})")
+    _fp8_cache_contiguous(cache, "attn_decode_ragged_multi_fp8")
+    if split_rows is None:
+        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % DECODE_MULTI_CHUNK != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{DECODE_MULTI_CHUNK} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    # the bf16 op's workspace: same shape key, and the ops run in stream order
+    key = (B, Hkv, T * G, D, nsplit, q.device.index)
+    ws = _MULTI_WS.get(key)
+    if ws is None:
+        ws = _MULTI_WS[key] = torch.empty(
+            B * Hkv, nsplit, T * G * (D + 2), device=q.device,
+            dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_decode_ragged_multi_fp8(
+            stream_of(q), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), ptr(o), ptr(ws), ptr(lens),
+            ptr(n_new), B, T, H, Hkv, Smax, D, split_rows, D**-0.5,
+        ),
+        "attn_decode_ragged_multi_fp8",
+    )
+    return o
+
+
+def decode_qkv_append_multi_fp8(qkv, cos, sin, cache: KVCacheFp8, pos, n_new,
+                                n_heads: int, n_kv_heads: int) -> torch.Tensor:
+    """decode_qkv_append_multi into an fp8 cache: the same inputs, dead-token
+    rule and rotated q [B,T,H,D] (bit-identical); k (rotated, rounded to
+    qkv's dtype) and v of token t are quantised per head row into row
+    pos[b] + t of `cache`, as decode_qkv_append_fp8 does for one token."""
+    _check_fp8_cache(cache, "decode_qkv_append_multi_fp8")
+    H, Hkv = n_heads, n_kv_heads
+    _, Smax, Hkv_c, D = cache.k.shape
+    R = cos.shape[0]
+    if qkv.dim() != 3 or qkv.shape[2] != (H + 2 * Hkv) * D or Hkv_c != Hkv:
+        raise ValueError(f"decode_qkv_append_multi_fp8: qkv {tuple(qkv.shape)} "
+                         f"does not match heads={H}, kv_heads={Hkv}, "
+                         f"head_dim={D}")
+    B, T = qkv.shape[:2]
+    for name, v in (("pos", pos), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != qkv.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on qkv's device")
+    if not _is_hip(qkv):
+        q = torch.zeros(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+        x = qkv.view(B, T, H + 2 * Hkv, D)
+        for b, (p0, n) in enumerate(zip(pos.tolist(), n_new.tolist())):
+            for t in range(T):
+                p = p0 + t
+                if p0 < 0 or t >= n or p >= min(Smax, R):
+                    continue
+                xt = x[b:b + 1, t:t + 1]
+                q[b, t] = ref.apply_rope(xt[:, :, :H], cos, sin, p)[0, 0]
+                kq, ks = _kv_quant(
+                    ref.apply_rope(xt[:, :, H:H + Hkv], cos, sin, p)[0, 0])
+                vq, vs = _kv_quant(x[b, t, H + Hkv:])
+                cache.k[b, p], cache.k_scale[b, p] = kq, ks
+                cache.v[b, p], cache.v_scale[b, p] = vq, vs
+        return q
+    if D not in (64, 128) or not 1 <= T <= _MULTI_MAX_T:
+        raise NotImplementedError(
+            f"decode_qkv_append_multi_fp8 needs head_dim in {{64, 128}} and "
+            f"1 <= T <= {_MULTI_MAX_T} (got head_dim={D}, T={T})")
+    _fp8_cache_contiguous(cache, "decode_qkv_append_multi_fp8")
+    qkv = qkv.contiguous()
+    q = torch.empty(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_decode_qkv_append_multi_fp8(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), ptr(cos), ptr(sin),
+            ptr(pos), ptr(n_new), B, T, H, Hkv, D, Smax, R,
+        ),
+        "decode_qkv_append_multi_fp8",
+    )
+    return q
+
+
 def mfma_probe32(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     """32x32x16 bf16 MFMA single-tile matmul (layout verification)."""
     C = torch.empty(32, 32, device=A.device, dtype=torch.float32)

@@ -3,6 +3,11 @@ T calls of attn_decode_ragged (what verifying T drafted tokens costs without
 it), and against one single-token call (the byte-count expectation).
 
   python tools/perf_decode_multi.py
+  python tools/perf_decode_multi.py --fp8
+
+With --fp8 the three paths are one T-token attn_decode_ragged_multi_fp8 call
+over an fp8 (e4m3) cache, one bf16 T-token call at the same shape, and T
+calls of attn_decode_ragged_fp8.
 
 The parent process never touches the GPU: every (B, L) shape runs in a
 fresh child process under its own time limit, `--procs` times over, and the
@@ -36,16 +41,21 @@ def _fmt(xs, digits=1):
             f"({min(xs):.{digits}f}-{max(xs):.{digits}f})")
 
 
-def step(B, L, iters, repeats):
+def step(B, L, iters, repeats, fp8=False):
     import torch
 
     from prime_amd import ops
 
     torch.manual_seed(0)
     dev = "cuda"
-    nbuf = max(2, -(-(1 << 30) // (2 * B * L * HKV * D * 2)))
+    # >= 1 GiB of the smaller (fp8) caches too
+    nbuf = max(2, -(-(1 << 30) // (2 * B * L * HKV * D * (1 if fp8 else 2))))
     kcs = [torch.randn(B, L, HKV, D, device=dev).bfloat16() for _ in range(nbuf)]
     vcs = [torch.randn(B, L, HKV, D, device=dev).bfloat16() for _ in range(nbuf)]
+    c8s = []
+    for kc, vc in zip(kcs, vcs) if fp8 else ():
+        c8s.append(ops.kv_cache_fp8(B, L, HKV, D, dev))
+        ops.kv_store_fp8(c8s[-1], kc, vc, 0)
     out = {}
     for T in TS:
         q = torch.randn(B, T, H, D, device=dev).bfloat16()
@@ -66,8 +76,20 @@ def step(B, L, iters, repeats):
             return ops.attn_decode_ragged(qs[-1], kcs[i % nbuf], vcs[i % nbuf],
                                           lens[-1])
 
-        fns = {"multi": multi, "singles": singles, "one": one}
-        diff = (multi(0).float() - torch.stack(singles(0), 1).float()).abs().max()
+        def multi_fp8(i):
+            return ops.attn_decode_ragged_multi_fp8(q, c8s[i % nbuf], lens[0],
+                                                    n_new)
+
+        def singles_fp8(i):
+            return [ops.attn_decode_ragged_fp8(qs[t], c8s[i % nbuf], lens[t])
+                    for t in range(T)]
+
+        if fp8:
+            fns = {"multi": multi_fp8, "singles": singles_fp8, "one": multi}
+        else:
+            fns = {"multi": multi, "singles": singles, "one": one}
+        diff = (fns["multi"](0).float()
+                - torch.stack(fns["singles"](0), 1).float()).abs().max()
         for fn in fns.values():  # warm every path
             for i in range(3):
                 fn(i)
@@ -94,6 +116,9 @@ def main():
     ap.add_argument("--procs", type=int, default=3, help="process repeats")
     ap.add_argument("--step-limit", type=float, default=120.0,
                     help="time limit of each child process in seconds")
+    ap.add_argument("--fp8", action="store_true",
+                    help="time the fp8-cache T-token op against the bf16 "
+                    "T-token op and T fp8 single-token calls")
     ap.add_argument("--step", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.step:  # child: one shape, one JSON line
@@ -102,21 +127,27 @@ def main():
         if not torch.cuda.is_available():
             raise SystemExit("perf_decode_multi needs a GPU")
         s = json.loads(args.step)
-        print(json.dumps(step(s["B"], s["L"], s["iters"], s["repeats"])))
+        print(json.dumps(step(s["B"], s["L"], s["iters"], s["repeats"],
+                              s.get("fp8", False))))
         return
     print(f"H={H} Hkv={HKV} D={D} bf16, {args.iters} calls per timing, "
           f"{args.repeats} alternating repeats x {args.procs} processes; "
           f"us, median (min-max)")
-    print("| B | L | T | one T-token call | T single-token calls | one "
-          "single-token call | multi vs T singles | multi / one single | "
-          "max abs diff |")
+    if args.fp8:
+        print("| B | L | T | one fp8 T-token call | T fp8 single-token calls | "
+              "one bf16 T-token call | fp8 multi vs T fp8 singles | fp8 multi "
+              "/ bf16 multi | max abs diff |")
+    else:
+        print("| B | L | T | one T-token call | T single-token calls | one "
+              "single-token call | multi vs T singles | multi / one single | "
+              "max abs diff |")
     print("|---|---|---|---|---|---|---|---|---|")
     for B, L in SHAPES:
         acc = {}
         for _ in range(args.procs):
             cmd = [sys.executable, str(Path(__file__).resolve()), "--step",
                    json.dumps({"B": B, "L": L, "iters": args.iters,
-                               "repeats": args.repeats})]
+                               "repeats": args.repeats, "fp8": args.fp8})]
             r = subprocess.run(cmd, capture_output=True, text=True,
                                timeout=args.step_limit)
             if r.returncode != 0:
