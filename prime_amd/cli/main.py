@@ -720,6 +720,10 @@ def generate_cmd(
         "prompt-lookup speculative decoding: draft this many tokens per step "
         "and verify them in one multi-token decode pass (greedy sequences, "
         "bf16 or fp8 cache; runs as a ragged batch)")),
+    prefill_chunk: int = typer.Option(0, "--prefill-chunk", min=0, help=(
+        "chunked ragged prefill: feed the prompts to the cache in steps of "
+        "this many tokens (a multiple of 8, bf16 cache; runs as a ragged "
+        "batch) instead of one prefill padded to the longest prompt")),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch
@@ -758,7 +762,7 @@ def generate_cmd(
     else:
         groups = [g for pt in prompt_tokens for g in pt.split(";") if g.strip()]
         prompts = [[int(t) for t in g.split(",")] for g in groups]
-    if len(prompts) > 1 or kv_dtype != "bf16" or lookahead:
+    if len(prompts) > 1 or kv_dtype != "bf16" or lookahead or prefill_chunk:
         # several prompts of different lengths: one ragged batch, one output
         # line (prompt + new tokens) per prompt; the fp8 cache and lookahead
         # decoding exist on the ragged path only, so they take a single
@@ -767,7 +771,7 @@ def generate_cmd(
 
         outs = generate_batch(m, prompts, max_new, temperature=temperature,
                               top_k=top_k, seed=seed, kv_dtype=kv_dtype,
-                              lookahead=lookahead)
+                              lookahead=lookahead, prefill_chunk=prefill_chunk)
         for p_ids, new in zip(prompts, outs):
             if tok is not None:
                 from ..utils.tokenizer import decode as tok_decode

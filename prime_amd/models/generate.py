@@ -181,6 +181,7 @@ def generate_batch(
     use_graph: bool = True,
     kv_dtype: str = "bf16",
     lookahead: int = 0,
+    prefill_chunk: int = 0,
 ) -> list[list[int]]:
     """Ragged batched generation: `prompts` is a list of token-id lists of
     different lengths; returns the NEW tokens of each. max_new_tokens,
@@ -214,8 +215,21 @@ def generate_batch(
     sequences take one token per step in the same batch. The host writes
     the step's tokens, positions and row counts; the graph is captured once
     per (batch bucket, cache-length bucket, device, T, kv_dtype). With an fp8
-    cache it needs a model on the GPU."""
+    cache it needs a model on the GPU.
+
+    prefill_chunk = C > 0 (a multiple of 8, bf16 cache only) replaces the
+    padded flash prefill: the prompts enter the ragged cache in steps of C
+    tokens, each sequence at its own position, through the chunked ragged
+    prefill kernels (ops.prefill_qkv_append + ops.attn_prefill_ragged). A
+    short prompt costs its own length, not the longest one's. Runs eagerly."""
     lookahead = int(lookahead)
+    prefill_chunk = int(prefill_chunk)
+    if prefill_chunk < 0 or prefill_chunk % 8 != 0:
+        raise ValueError(f"prefill_chunk must be 0 or a positive multiple of 8 "
+                         f"(got {prefill_chunk})")
+    if prefill_chunk and kv_dtype != "bf16":
+        raise ValueError("prefill_chunk needs kv_dtype='bf16': chunked prefill "
+                         "reads a bf16 cache")
     if not 0 <= lookahead <= 7:
         raise ValueError(f"lookahead must be in 0..7 (got {lookahead})")
     if kv_dtype not in KV_DTYPES:
@@ -313,17 +327,21 @@ def generate_batch(
             if len(out[b]) >= max_new[b] or t in stops:
                 done[b] = True
 
-    # ---- prefill the real sequences (views of the first n cache slots)
-    Lp = _pad64(max(L0))
-    padded = torch.zeros(n, Lp, dtype=torch.int64)
-    for b in range(n):
-        padded[b, :L0[b]] = torch.tensor(prompts[b], dtype=torch.int64)
-    padded = padded.to(dev)
-    pre = [ops.KVCacheFp8(*(t[:n] for t in c)) if isinstance(c, ops.KVCacheFp8)
-           else (c[0][:n], c[1][:n]) for c in caches]
-    h = model(padded, caches=pre, pos=0)
-    last = torch.tensor([l - 1 for l in L0], device=dev)
-    logits = model.lm_head(h[torch.arange(n, device=dev), last])
+    if prefill_chunk:
+        logits = model.lm_head(
+            prefill_chunked(model, caches, prompts, prefill_chunk))
+    else:
+        # ---- prefill the real sequences (views of the first n cache slots)
+        Lp = _pad64(max(L0))
+        padded = torch.zeros(n, Lp, dtype=torch.int64)
+        for b in range(n):
+            padded[b, :L0[b]] = torch.tensor(prompts[b], dtype=torch.int64)
+        padded = padded.to(dev)
+        pre = [ops.KVCacheFp8(*(t[:n] for t in c)) if isinstance(c, ops.KVCacheFp8)
+               else (c[0][:n], c[1][:n]) for c in caches]
+        h = model(padded, caches=pre, pos=0)
+        last = torch.tensor([l - 1 for l in L0], device=dev)
+        logits = model.lm_head(h[torch.arange(n, device=dev), last])
     live = [b for b in range(n) if not done[b]]
     accept(pick(logits, live))
 
@@ -360,6 +378,38 @@ def generate_batch(
         if any(done[b] for b in live):
             write_state()  # retire finished sequences to idle slots
     return out
+
+
+@torch.no_grad()
+def prefill_chunked(model, caches, prompts, chunk: int) -> torch.Tensor:
+    """Chunked ragged prefill: write `prompts` (token-id lists of different
+    lengths) into the first len(prompts) slots of the bf16 `caches`
+    [(k, v) per layer, each [Bk,Smax,Hkv,D]] in steps of `chunk` tokens and
+    return the hidden state at each prompt's last token, [len(prompts), dim].
+    At every step slot b takes min(chunk, remaining_b) tokens at pos =
+    done_b with lens = done_b + 1; finished and padding slots are idle
+    (lens = 0, n_new = 0)."""
+    dev = caches[0][0].device
+    Bk, n = caches[0][0].shape[0], len(prompts)
+    L = [len(p) for p in prompts]
+    last = [None] * n
+    for done in range(0, max(L), chunk):
+        tok = torch.zeros(Bk, chunk, dtype=torch.int64)
+        pos = torch.full((Bk,), -1, dtype=torch.int32)
+        nn = torch.zeros(Bk, dtype=torch.int32)
+        for b in range(n):
+            r = min(chunk, L[b] - done)
+            if r > 0:
+                tok[b, :r] = torch.tensor(prompts[b][done:done + r],
+                                          dtype=torch.int64)
+                pos[b], nn[b] = done, r
+        seq_pos = {"pos": pos.to(dev), "lens": ((pos + 1) * (nn > 0)).to(dev),
+                   "n_new": nn.to(dev)}
+        h = model(tok.to(dev), caches=caches, seq_pos=seq_pos)
+        for b in range(n):
+            if 0 < L[b] - done <= chunk:  # the prompt ends in this chunk
+                last[b] = h[b, L[b] - done - 1]
+    return torch.stack(last)
 
 
 def _ragged_state(caches, Bk, dev):

@@ -69,7 +69,14 @@ class Attention(nn.Module):
                     or self.sp_group is not None:
                 raise ValueError("seq_pos cannot be combined with doc_start, "
                                  "pos_dev or sequence parallelism")
+            # a chunk the verification kernels do not take (T > 8 or more
+            # than 64 query rows per kv head) is a prefill chunk
+            chunk = S > 8 or S * (cfg.n_heads // cfg.n_kv_heads) > 64
             if isinstance(cache, ops.KVCacheFp8):
+                if chunk:
+                    raise NotImplementedError(
+                        f"a {S}-token chunk (seq_pos with n_new) over an fp8 "
+                        "KV cache: chunked prefill reads a bf16 cache")
                 # pinned by test_decode_multi_cpu.py::test_model_guards
                 if not cache.k.is_cuda:
                     raise NotImplementedError(
@@ -82,6 +89,13 @@ class Attention(nn.Module):
                     q, cache, seq_pos["lens"], seq_pos["n_new"])
                 return self.wo(o.reshape(B, S, cfg.n_heads * hd))
             kc, vc = cache
+            if chunk and x.is_cuda:
+                q = ops.prefill_qkv_append(
+                    self.wqkv(x), cos, sin, kc, vc, seq_pos["pos"],
+                    seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)
+                o = ops.attn_prefill_ragged(q, kc, vc, seq_pos["lens"],
+                                            seq_pos["n_new"])
+                return self.wo(o.reshape(B, S, cfg.n_heads * hd))
             q = ops.decode_qkv_append_multi(
                 self.wqkv(x), cos, sin, kc, vc, seq_pos["pos"],
                 seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)

@@ -56,7 +56,12 @@ _SIGS = {
     "prime_attn_decode_ragged_multi": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 7 + [ctypes.c_double],
     "prime_decode_multi_chunk": [],
     "prime_decode_qkv_append_multi": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 7,
-    "prime_attn_decode_ragged_fp8": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 6 + [ctypes.c_double],
+    "prime_attn_prefill_ragged": [ctypes.c_void_p] * 8 + [ctypes.c_int64] * 7 + [ctypes.c_double],
+    "prime_prefill_q_rows": [],
+    "prime_prefill_key_tile": [],
+    "prime_prefill_qkv_append": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 7,
+    "prime_tr16_probe": [ctypes.c_void_p] * 3,
+    "prime_attn_decode_ragged_fp8":[ctypes.c_void_p] * 9 + [ctypes.c_int64] * 6 + [ctypes.c_double],
     "prime_decode_qkv_append_fp8": [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 6,
     "prime_kv_store_fp8": [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 6,
     "prime_attn_decode_ragged_multi_fp8": [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 7 + [ctypes.c_double],

@@ -179,3 +179,24 @@ PRIME_API int prime_decode_qkv_append_multi(
                      (int)H, (int)Hkv, (int)D, (int)Smax, (int)T, 1.f);
   return (int)hipGetLastError();
 }
+
+// The same pass for a prefill chunk: any TN >= 1 (the kernel is TN-agnostic;
+// the entry above keeps its cap for the verification path).
+PRIME_API int prime_prefill_qkv_append(
+    hipStream_t stream, const void* qkv, void* qout, void* kc, void* vc,
+    const void* cos_t, const void* sin_t, const void* pos, const void* n_new,
+    int64_t B, int64_t TN, int64_t H, int64_t Hkv, int64_t D, int64_t Smax,
+    int64_t T) {
+  if ((D != 64 && D != 128) || B < 1 || TN < 1 || H < 1 || Hkv < 1 ||
+      Smax < 1 || T < 1 || Smax > 0x7fffffff || T > 0x7fffffff ||
+      TN > 0x7fffffff || !pos || !n_new)
+    return hipErrorInvalidValue;
+  const int64_t nrows = B * TN * (H + 2 * Hkv);
+  const int grid = prime_grid(nrows * (D / 8), 256);
+  hipLaunchKernelGGL(decode_qkv_append_multi_kernel, dim3(grid), dim3(256), 0,
+                     stream, (const bf16*)qkv, (bf16*)qout, (bf16*)kc,
+                     (bf16*)vc, (const float*)cos_t, (const float*)sin_t,
+                     (const int*)pos, (const int*)n_new, nrows, (int)TN,
+                     (int)H, (int)Hkv, (int)D, (int)Smax, (int)T, 1.f);
+  return (int)hipGetLastError();
+}

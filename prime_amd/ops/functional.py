@@ -1439,6 +1439,151 @@ def decode_qkv_append_multi(qkv, cos, sin, k_cache, v_cache, pos, n_new,
     return q
 
 
+# ------------------------------------------ chunked ragged prefill (MFMA)
+# attn_prefill_ragged is the compute-bound sibling of the multi-token decode:
+# a workgroup owns PREFILL_Q_ROWS query rows (t*G + g) of one (b, kv head)
+# and walks the keys in PREFILL_KEY_TILE steps; split_rows is a multiple of
+# the key tile.
+PREFILL_Q_ROWS = 128
+PREFILL_KEY_TILE = 64
+_PREFILL_WS: dict = {}  # (B, Hkv, T*G, D, nsplit, device) -> fp32 partials
+
+
+def prefill_ragged_split(B: int, Hkv: int, T: int, G: int, Smax: int,
+                         n_cu: int = 256) -> int:
+    """Rows per key split of attn_prefill_ragged: a multiple of
+    PREFILL_KEY_TILE that depends on the launch shape only (stable under
+    graph replay). The keys are split only when the q-tiles cannot fill the
+    machine: with q-tiles * B * Hkv >= 2 workgroups per CU it is Smax rounded
+    up (one split, no workspace); a split is never shorter than 4 key tiles."""
+    tiles = -(-T * G // PREFILL_Q_ROWS) * B * Hkv
+    steps = -(-Smax // PREFILL_KEY_TILE)
+    want = max(1, min(steps // 4, -(-2 * n_cu // tiles)))
+    return -(-steps // want) * PREFILL_KEY_TILE
+
+
+def attn_prefill_ragged(q, k_cache, v_cache, lens, n_new,
+                        split_rows=None) -> torch.Tensor:
+    """Block attention over the KV cache for a chunk of T new tokens per
+    sequence: q [B,T,H,D] against caches [B,Smax,Hkv,D] that already hold the
+    new tokens' rows. The contract is attn_decode_ragged_multi's without the
+    T limit: with L0 = clamp(lens[b], 0, Smax) and n = clamp(n_new[b], 0,
+    min(T, Smax - L0 + 1)) (n = 0 if L0 == 0), query t < n attends to rows
+    [0, L0 + t), query t >= n gives exact zeros, and no row at or beyond
+    L0 + n - 1 is read. `lens` and `n_new` are int32 [B] device tensors read
+    at kernel time. Supported: D in {64, 128}, G = H/Hkv in {1, 2, 4, 8},
+    1 <= T <= Smax. `split_rows` overrides prefill_ragged_split (a multiple
+    of PREFILL_KEY_TILE)."""
+    _reject_fp8(k_cache, "attn_prefill_ragged")
+    if q.dim() != 4:
+        raise ValueError("attn_prefill_ragged needs q [B,T,H,D]")
+    B, T, H, D = q.shape
+    _, Smax, Hkv, _ = k_cache.shape
+    for name, v in (("lens", lens), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        o = torch.zeros_like(q)
+        for b, (L, n) in enumerate(zip(lens.tolist(), n_new.tolist())):
+            L0, n = _multi_live(L, n, T, Smax)
+            for t in range(n):
+                o[b, t] = ref.attention(
+                    q[b:b + 1, t:t + 1], k_cache[b:b + 1, :L0 + t],
+                    v_cache[b:b + 1, :L0 + t], causal=False)[0, 0]
+        return o
+    G = H // Hkv if H % Hkv == 0 else 0
+    if D not in (64, 128) or G not in _RAGGED_GROUPS or not 1 <= T <= Smax:
+        raise NotImplementedError(
+            f"attn_prefill_ragged needs head_dim in {{64, 128}}, a GQA group "
+            f"size in {_RAGGED_GROUPS} and 1 <= T <= Smax (got head_dim={D}, "
+            f"heads={H}, kv_heads={Hkv}, T={T}, Smax={Smax})")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attn_prefill_ragged needs contiguous KV caches")
+    if split_rows is None:
+        split_rows = prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % PREFILL_KEY_TILE != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{PREFILL_KEY_TILE} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    ws = None
+    if nsplit > 1:
+        # one workspace per shape, reused: a captured graph sees stable pointers
+        key = (B, Hkv, T * G, D, nsplit, q.device.index)
+        ws = _PREFILL_WS.get(key)
+        if ws is None:
+            ws = _PREFILL_WS[key] = torch.empty(
+                B * Hkv * nsplit * T * G * (D + 2), device=q.device,
+                dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_prefill_ragged(
+            stream_of(q), ptr(q), ptr(k_cache), ptr(v_cache), ptr(o), ptr(ws),
+            ptr(lens), ptr(n_new), B, T, H, Hkv, Smax, D, split_rows, D**-0.5,
+        ),
+        "attn_prefill_ragged",
+    )
+    return o
+
+
+def prefill_qkv_append(qkv, cos, sin, k_cache, v_cache, pos, n_new,
+                       n_heads: int, n_kv_heads: int) -> torch.Tensor:
+    """decode_qkv_append_multi for a prefill chunk of any length: qkv
+    [B,T,(H+2Hkv)*D]; token t of slot b is rotated at pos[b] + t (bit-identical
+    to apply_rope(..., pos_offset=pos[b] + t)), its k and v go to cache row
+    pos[b] + t, and the rotated q is returned as [B,T,H,D]. A token is dead
+    if pos[b] < 0, t >= n_new[b] or pos[b] + t >= min(Smax, len(cos)): it
+    writes no cache row and its q rows are zeros."""
+    _reject_fp8(k_cache, "prefill_qkv_append")
+    H, Hkv = n_heads, n_kv_heads
+    _, Smax, Hkv_c, D = k_cache.shape
+    R = cos.shape[0]
+    if qkv.dim() != 3 or qkv.shape[2] != (H + 2 * Hkv) * D or Hkv_c != Hkv:
+        raise ValueError(f"prefill_qkv_append: qkv {tuple(qkv.shape)} does "
+                         f"not match heads={H}, kv_heads={Hkv}, head_dim={D}")
+    B, T = qkv.shape[:2]
+    for name, v in (("pos", pos), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != qkv.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on qkv's device")
+    if not _is_hip(qkv):
+        q = torch.zeros(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+        x = qkv.view(B, T, H + 2 * Hkv, D)
+        for b, (p0, n) in enumerate(zip(pos.tolist(), n_new.tolist())):
+            for t in range(T):
+                p = p0 + t
+                if p0 < 0 or t >= n or p >= min(Smax, R):
+                    continue
+                xt = x[b:b + 1, t:t + 1]
+                q[b, t] = ref.apply_rope(xt[:, :, :H], cos, sin, p)[0, 0]
+                k_cache[b, p] = ref.apply_rope(xt[:, :, H:H + Hkv], cos, sin, p)[0, 0]
+                v_cache[b, p] = x[b, t, H + Hkv:]
+        return q
+    if D not in (64, 128) or T < 1:
+        raise NotImplementedError(
+            f"prefill_qkv_append needs head_dim in {{64, 128}} and T >= 1 "
+            f"(got head_dim={D}, T={T})")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("prefill_qkv_append needs contiguous KV caches")
+    qkv = qkv.contiguous()
+    q = torch.empty(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_prefill_qkv_append(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(k_cache), ptr(v_cache),
+            ptr(cos), ptr(sin), ptr(pos), ptr(n_new), B, T, H, Hkv, D, Smax, R,
+        ),
+        "prefill_qkv_append",
+    )
+    return q
+
+
+def tr16_probe(src: torch.Tensor) -> torch.Tensor:
+    """src [64,64] bf16 -> its transpose through attn_prefill_ragged's V path
+    (swizzled LDS stage + transposing LDS read): lane-map verification."""
+    dst = torch.empty_like(src)
+    check(lib().prime_tr16_probe(stream_of(src), ptr(src), ptr(dst)), "tr16_probe")
+    return dst
+
+
 # ------------------------------------------------------------ fp8 KV cache
 class KVCacheFp8(NamedTuple):
     """One layer's fp8 KV cache. k, v: float8_e4m3fn [B,Smax,Hkv,D];

@@ -53,7 +53,8 @@ class ChatRequest(BaseModel):
 
 
 def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
-               batch_window_ms: float = 5.0, kv_dtype: str = "bf16"):
+               batch_window_ms: float = 5.0, kv_dtype: str = "bf16",
+               prefill_chunk: int = 0):
     from fastapi import FastAPI, HTTPException
 
     from .models import generate as gen_mod
@@ -63,6 +64,10 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
     if kv_dtype not in gen_mod.KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {gen_mod.KV_DTYPES} (got "
                          f"{kv_dtype!r})")
+    if prefill_chunk < 0 or prefill_chunk % 8 != 0 or \
+            (prefill_chunk and kv_dtype != "bf16"):
+        raise ValueError("prefill_chunk must be 0 or a positive multiple of 8, "
+                         "and needs kv_dtype='bf16'")
     app = FastAPI(title="prime-amd inference")
     dev = next(model.parameters()).device
     pending: queue.Queue = queue.Queue()
@@ -85,7 +90,8 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                     temperature=[r.temperature for _, r, _ in items],
                     top_k=[r.top_k for _, r, _ in items],
                     seed=[r.seed for _, r, _ in items],
-                    stop_token_ids=list(stop), kv_dtype=kv_dtype)
+                    stop_token_ids=list(stop), kv_dtype=kv_dtype,
+                    prefill_chunk=prefill_chunk)
                 for (_, _, fut), new in zip(items, outs):
                     fut.set_result(new)
             except Exception as e:  # noqa: BLE001 - reported to every caller
