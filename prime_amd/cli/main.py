@@ -722,8 +722,8 @@ def generate_cmd(
         "bf16 or fp8 cache; runs as a ragged batch)")),
     prefill_chunk: int = typer.Option(0, "--prefill-chunk", min=0, help=(
         "chunked ragged prefill: feed the prompts to the cache in steps of "
-        "this many tokens (a multiple of 8, bf16 cache; runs as a ragged "
-        "batch) instead of one prefill padded to the longest prompt")),
+        "this many tokens (a multiple of 8, bf16 or fp8 cache; runs as a "
+        "ragged batch) instead of one prefill padded to the longest prompt")),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch

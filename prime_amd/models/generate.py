@@ -217,19 +217,20 @@ def generate_batch(
     per (batch bucket, cache-length bucket, device, T, kv_dtype). With an fp8
     cache it needs a model on the GPU.
 
-    prefill_chunk = C > 0 (a multiple of 8, bf16 cache only) replaces the
-    padded flash prefill: the prompts enter the ragged cache in steps of C
-    tokens, each sequence at its own position, through the chunked ragged
-    prefill kernels (ops.prefill_qkv_append + ops.attn_prefill_ragged). A
-    short prompt costs its own length, not the longest one's. Runs eagerly."""
+    prefill_chunk = C > 0 (a multiple of 8) replaces the padded flash
+    prefill: the prompts enter the ragged cache in steps of C tokens, each
+    sequence at its own position, through the chunked ragged prefill kernels
+    (ops.prefill_qkv_append + ops.attn_prefill_ragged, or their _fp8 siblings
+    with kv_dtype "fp8", which needs a model on the GPU). A short prompt costs
+    its own length, not the longest one's. Runs eagerly. Over an fp8 cache a
+    chunk attends to the QUANTISED rows, its own included, so the first new
+    token is that of the quantised cache, not that of the bf16 cache as with
+    the padded prefill."""
     lookahead = int(lookahead)
     prefill_chunk = int(prefill_chunk)
     if prefill_chunk < 0 or prefill_chunk % 8 != 0:
         raise ValueError(f"prefill_chunk must be 0 or a positive multiple of 8 "
                          f"(got {prefill_chunk})")
-    if prefill_chunk and kv_dtype != "bf16":
-        raise ValueError("prefill_chunk needs kv_dtype='bf16': chunked prefill "
-                         "reads a bf16 cache")
     if not 0 <= lookahead <= 7:
         raise ValueError(f"lookahead must be in 0..7 (got {lookahead})")
     if kv_dtype not in KV_DTYPES:
@@ -239,6 +240,10 @@ def generate_batch(
     cfg = model.cfg
     p0 = next(model.parameters())
     dev, dtype = p0.device, p0.dtype
+    if prefill_chunk and kv_dtype != "bf16" and dev.type != "cuda":
+        raise ValueError("prefill_chunk with kv_dtype='fp8' needs a model on "
+                         "the GPU: chunked prefill over an fp8 cache has no "
+                         "host path")
     if lookahead and kv_dtype != "bf16" and dev.type != "cuda":
         # the model's guard (Attention.forward), raised before any work
         raise NotImplementedError("lookahead decoding over an fp8 KV cache "
@@ -383,13 +388,16 @@ def generate_batch(
 @torch.no_grad()
 def prefill_chunked(model, caches, prompts, chunk: int) -> torch.Tensor:
     """Chunked ragged prefill: write `prompts` (token-id lists of different
-    lengths) into the first len(prompts) slots of the bf16 `caches`
-    [(k, v) per layer, each [Bk,Smax,Hkv,D]] in steps of `chunk` tokens and
-    return the hidden state at each prompt's last token, [len(prompts), dim].
-    At every step slot b takes min(chunk, remaining_b) tokens at pos =
-    done_b with lens = done_b + 1; finished and padding slots are idle
-    (lens = 0, n_new = 0)."""
-    dev = caches[0][0].device
+    lengths) into the first len(prompts) slots of `caches` [(k, v) or an
+    ops.KVCacheFp8 per layer, each k [Bk,Smax,Hkv,D]] in steps of `chunk`
+    tokens and return the hidden state at each prompt's last token,
+    [len(prompts), dim]. At every step slot b takes min(chunk, remaining_b)
+    tokens at pos = done_b with lens = done_b + 1; finished and padding slots
+    are idle (lens = 0, n_new = 0). Over fp8 caches (GPU only) every chunk
+    attends to the quantised rows, its own included: the result is that of
+    the quantised cache, not of the unquantised k and v as with the padded
+    prefill."""
+    dev = caches[0][0].device  # k of a (k, v) pair or of a KVCacheFp8
     Bk, n = caches[0][0].shape[0], len(prompts)
     L = [len(p) for p in prompts]
     last = [None] * n

@@ -73,15 +73,19 @@ class Attention(nn.Module):
             # than 64 query rows per kv head) is a prefill chunk
             chunk = S > 8 or S * (cfg.n_heads // cfg.n_kv_heads) > 64
             if isinstance(cache, ops.KVCacheFp8):
-                if chunk:
-                    raise NotImplementedError(
-                        f"a {S}-token chunk (seq_pos with n_new) over an fp8 "
-                        "KV cache: chunked prefill reads a bf16 cache")
                 # pinned by test_decode_multi_cpu.py::test_model_guards
                 if not cache.k.is_cuda:
                     raise NotImplementedError(
-                        "multi-token decode (seq_pos with n_new) over an fp8 "
-                        "KV cache runs on the GPU only")
+                        "multi-token decode and chunked prefill (seq_pos with "
+                        "n_new) over an fp8 KV cache run on the GPU only")
+                if chunk:
+                    # attends to the QUANTISED rows, the chunk's own included
+                    q = ops.prefill_qkv_append_fp8(
+                        self.wqkv(x), cos, sin, cache, seq_pos["pos"],
+                        seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)
+                    o = ops.attn_prefill_ragged_fp8(
+                        q, cache, seq_pos["lens"], seq_pos["n_new"])
+                    return self.wo(o.reshape(B, S, cfg.n_heads * hd))
                 q = ops.decode_qkv_append_multi_fp8(
                     self.wqkv(x), cos, sin, cache, seq_pos["pos"],
                     seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)

@@ -589,16 +589,11 @@ __global__ __launch_bounds__(256) void decode_qkv_append_multi_fp8_kernel(
   }
 }
 
-// TN: new tokens per sequence in qkv; T: rows of the cos / sin tables.
-PRIME_API int prime_decode_qkv_append_multi_fp8(
+static int dm8_append_launch(
     hipStream_t stream, const void* qkv, void* qout, void* kc, void* vc,
     void* k_scale, void* v_scale, const void* cos_t, const void* sin_t,
     const void* pos, const void* n_new, int64_t B, int64_t TN, int64_t H,
     int64_t Hkv, int64_t D, int64_t Smax, int64_t T) {
-  if ((D != 64 && D != 128) || B < 1 || TN < 1 || TN > 8 || H < 1 ||
-      Hkv < 1 || Smax < 1 || T < 1 || Smax > 0x7fffffff || T > 0x7fffffff ||
-      !pos || !n_new || !k_scale || !v_scale)
-    return hipErrorInvalidValue;
   const int64_t nrows = B * TN * (H + 2 * Hkv);
   const int grid = prime_grid(nrows * (D / 8), 256);
   if (D == 128)
@@ -616,4 +611,33 @@ PRIME_API int prime_decode_qkv_append_multi_fp8(
                        (const int*)pos, (const int*)n_new, nrows, (int)TN,
                        (int)H, (int)Hkv, (int)Smax, (int)T, 1.f);
   return (int)hipGetLastError();
+}
+
+// TN: new tokens per sequence in qkv; T: rows of the cos / sin tables.
+PRIME_API int prime_decode_qkv_append_multi_fp8(
+    hipStream_t stream, const void* qkv, void* qout, void* kc, void* vc,
+    void* k_scale, void* v_scale, const void* cos_t, const void* sin_t,
+    const void* pos, const void* n_new, int64_t B, int64_t TN, int64_t H,
+    int64_t Hkv, int64_t D, int64_t Smax, int64_t T) {
+  if ((D != 64 && D != 128) || B < 1 || TN < 1 || TN > 8 || H < 1 ||
+      Hkv < 1 || Smax < 1 || T < 1 || Smax > 0x7fffffff || T > 0x7fffffff ||
+      !pos || !n_new || !k_scale || !v_scale)
+    return hipErrorInvalidValue;
+  return dm8_append_launch(stream, qkv, qout, kc, vc, k_scale, v_scale, cos_t,
+                           sin_t, pos, n_new, B, TN, H, Hkv, D, Smax, T);
+}
+
+// The same pass for a prefill chunk: any TN >= 1 (the kernel is TN-agnostic;
+// the entry above keeps its cap for the verification path).
+PRIME_API int prime_prefill_qkv_append_fp8(
+    hipStream_t stream, const void* qkv, void* qout, void* kc, void* vc,
+    void* k_scale, void* v_scale, const void* cos_t, const void* sin_t,
+    const void* pos, const void* n_new, int64_t B, int64_t TN, int64_t H,
+    int64_t Hkv, int64_t D, int64_t Smax, int64_t T) {
+  if ((D != 64 && D != 128) || B < 1 || TN < 1 || H < 1 || Hkv < 1 ||
+      Smax < 1 || T < 1 || Smax > 0x7fffffff || T > 0x7fffffff ||
+      TN > 0x7fffffff || !pos || !n_new || !k_scale || !v_scale)
+    return hipErrorInvalidValue;
+  return dm8_append_launch(stream, qkv, qout, kc, vc, k_scale, v_scale, cos_t,
+                           sin_t, pos, n_new, B, TN, H, Hkv, D, Smax, T);
 }

@@ -54,51 +54,12 @@
 //
 // This file is compiled without the packed fp32 VALU instructions
 // (ops/build.py, NO_PACKED_FP32).
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) short short8;
-typedef __attribute__((ext_vector_type(4))) short short4v;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) short4v lds_short4;
-typedef __attribute__((address_space(1))) const void g_void;
-
-#define PF_THREADS 256
-#define PF_Q_ROWS 128    // query rows (t*G + g) per workgroup, 32 per wave
-#define PF_KEY_TILE 64   // keys per step
-#define PF_NEG (-1e30f)
-
-// Clamped (L0, n) of slot b, the same in both kernels.
-__device__ __forceinline__ void pf_live(const int* __restrict__ lens,
-                                        const int* __restrict__ n_new, int b,
-                                        int T, int Smax, int& L0, int& n) {
-  L0 = min(max(lens[b], 0), Smax);
-  n = L0 == 0 ? 0 : min(max(n_new[b], 0), min(T, Smax - L0 + 1));
-}
-
-// ---- LDS images -----------------------------------------------------------
-// Both tiles are [64 keys][D] bf16, linear, with an XOR on the byte offset
-// inside the row, applied through the pre-swizzled SOURCE address (LDS-DMA
-// writes linearly). K: the 16 B slot XOR of attention.hip's swz16 (a 16 B
-// fragment read of 32 rows x 2 slots is conflict-free). V: the transposing
-// read takes, per 16 lanes, 4 consecutive rows x 32 contiguous bytes, and
-// the two 16-lane groups of a half wave sit side by side (64 B); XORing the
-// 64 B block index with the row's position among its 4 puts the four rows
-// in four different quarters of the 256 B bank line (D = 64: two rows share
-// a line, so the row pair's parity picks the block).
-template <int D>
-__device__ __forceinline__ int pf_kswz(int row) {
-  return (D == 128 ? (row & 15) : ((row >> 1) & 7)) << 4;
-}
-template <int D>
-__device__ __forceinline__ int pf_vswz(int row) {
-  return (D == 128 ? (row & 3) : ((row >> 1) & 1)) << 6;
-}
+#include "prefill_common.h"
 
 // Stage keys [kb, kb + 64) of one (b, kv head) into `tile`; rows past `last`
-// re-read row `last`. 256 lanes, 16 B each, D/32 rounds.
+// re-read row `last`. 256 lanes, 16 B each, D/32 rounds. The swizzle of the
+// image (prefill_common.h) is applied through the SOURCE address: LDS-DMA
+// writes linearly.
 template <int D, bool VTILE>
 __device__ __forceinline__ void pf_stage(const bf16* __restrict__ gbase,
                                          int64_t row_stride, int kb, int last,
@@ -121,55 +82,6 @@ __device__ __forceinline__ void pf_stage(const bf16* __restrict__ gbase,
 // s_waitcnt vmcnt(0): this wave's loads, LDS-DMA included, have landed
 __device__ __forceinline__ void pf_wait_loads() {
   __builtin_amdgcn_s_waitcnt(0x0F70);
-}
-
-template <int D>
-__device__ __forceinline__ short8 pf_kfrag(const bf16* tile, int row, int colb) {
-  return *reinterpret_cast<const short8*>(reinterpret_cast<const char*>(tile) +
-                                          row * (D * 2) +
-                                          (colb ^ pf_kswz<D>(row)));
-}
-
-// V^T fragment of the 32x32x16 MFMA from the [key][d] tile: the lane gets
-// V[key = ks*16 + hi*8 + j][d = dt*32 + lo], j = 0..7.
-// ds_read_b64_tr_b16, per group of 16 lanes (i = lane & 15): lane i gives the
-// address of 4 contiguous bf16; the 16 x 4 values are the 4 x 16 matrix
-// M[e][c] = (lane 4*e + c/4, element c%4), and lane i receives column i,
-// M[0..3][i]. So lanes 4e..4e+3 point at row (key) e, 16 consecutive d, and
-// every lane comes back with 4 consecutive keys at d = i. Two reads give the
-// 8 keys. HW-verified by tests/test_prefill_ragged_gpu.py::
-// test_transposing_read_probe with asymmetric data.
-template <int D>
-__device__ __forceinline__ short8 pf_vfrag(const bf16* tile, int ks, int dt,
-                                           int lane) {
-  const int i = lane & 15, g1 = (lane >> 4) & 1, hi = lane >> 5;
-  const int colb = (dt * 32 + g1 * 16 + (i & 3) * 4) * 2;
-  short4v x[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int row = ks * 16 + hi * 8 + h * 4 + (i >> 2);
-    const lds_char* p =
-        (const lds_char*)tile + row * (D * 2) + (colb ^ pf_vswz<D>(row));
-    x[h] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)p);
-  }
-  return short8{x[0][0], x[0][1], x[0][2], x[0][3],
-                x[1][0], x[1][1], x[1][2], x[1][3]};
-}
-
-__device__ __forceinline__ f32x16 pf_mfma(short8 a, short8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// two f32 -> one dword of 2 bf16, round to nearest even
-__device__ __forceinline__ unsigned pf_cvt_pk(float lo_, float hi_) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_), "v"(hi_));
-  return r;
-}
-
-// v_permlane32_swap_b32 a, b: a's lanes >= 32 swap with b's lanes < 32
-__device__ __forceinline__ void pf_swap32(unsigned& a, unsigned& b) {
-  asm volatile("v_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
 template <int D, int GSH>
@@ -204,24 +116,7 @@ __global__ __launch_bounds__(PF_THREADS, 2) void attn_prefill_ragged_kernel(
   float* ws_ml = ws + (int64_t)gridDim.y * nsplit * M * D + prow * 2;
 
   if (r0 >= r1) {  // block-uniform: nothing live here; no cache row touched
-    for (int i = tid; i < PF_Q_ROWS * (D / 8); i += PF_THREADS) {
-      const int row = row0 + i / (D / 8), c8 = (i % (D / 8)) * 8;
-      if (row >= M) break;
-      if (nsplit == 1) {
-        const int t = row >> GSH, g = row & (G - 1);
-        *reinterpret_cast<short8*>(
-            O + (((int64_t)b * T + t) * H + hkv * G + g) * D + c8) =
-            short8{0, 0, 0, 0, 0, 0, 0, 0};
-      } else {
-        float* p = ws_o + (int64_t)row * D + c8;
-        *reinterpret_cast<f32x4*>(p) = f32x4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<f32x4*>(p + 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c8 == 0) {
-          ws_ml[row * 2] = PF_NEG;
-          ws_ml[row * 2 + 1] = 0.f;
-        }
-      }
-    }
+    pf_write_empty<D, GSH>(O, ws_o, ws_ml, row0, M, nsplit, b, hkv, T, H, tid);
     return;
   }
 
@@ -331,27 +226,16 @@ __global__ __launch_bounds__(PF_THREADS, 2) void attn_prefill_ragged_kernel(
       }
     l_run += psum;  // this lane's half of the row; pair-reduced at the end
 
-    // ---- P^T fragments: per 16 keys, pack the two 4-value r-groups and
-    // swap halves with the partner lane: lanes < 32 end with keys 0..7,
-    // lanes >= 32 with keys 8..15 of the slice
+    // ---- P^T fragments (pf_pfrag): 16 keys each, natural key order
     short8 pa[4];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int kst = 0; kst < 2; ++kst) {
         const int g0 = 8 * kst, g1 = 8 * kst + 4;
-        unsigned x0 = pf_cvt_pk(st[t][g0 + 0], st[t][g0 + 1]);
-        unsigned x1 = pf_cvt_pk(st[t][g0 + 2], st[t][g0 + 3]);
-        unsigned y0 = pf_cvt_pk(st[t][g1 + 0], st[t][g1 + 1]);
-        unsigned y1 = pf_cvt_pk(st[t][g1 + 2], st[t][g1 + 3]);
-        pf_swap32(x0, y0);
-        pf_swap32(x1, y1);
-        short8 frag;
-        reinterpret_cast<unsigned*>(&frag)[0] = x0;
-        reinterpret_cast<unsigned*>(&frag)[1] = x1;
-        reinterpret_cast<unsigned*>(&frag)[2] = y0;
-        reinterpret_cast<unsigned*>(&frag)[3] = y1;
-        pa[t * 2 + kst] = frag;
+        pa[t * 2 + kst] = pf_pfrag(st[t][g0], st[t][g0 + 1], st[t][g0 + 2],
+                                   st[t][g0 + 3], st[t][g1], st[t][g1 + 1],
+                                   st[t][g1 + 2], st[t][g1 + 3]);
       }
     // ---- O^T += V^T . P^T
 #pragma unroll
@@ -362,71 +246,10 @@ __global__ __launch_bounds__(PF_THREADS, 2) void attn_prefill_ragged_kernel(
                             o_acc[dt]);
   }
 
-  // ---- epilogue: o_acc[dt][r] is d = dt*32 + (r&3) + 8*(r>>2) + 4*hi of
-  // query row lo
   l_run += __shfl_xor(l_run, 32, 64);
   if (myrow >= M) return;
-  if (nsplit == 1) {
-    const float inv = (live && l_run > 0.f) ? 1.f / l_run : 0.f;
-    bf16* orow = O + qo_off;
-#pragma unroll
-    for (int dt = 0; dt < DT32; ++dt)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        bf16x4 y;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          y.v[j] = f2bf(live ? o_acc[dt][rg * 4 + j] * inv : 0.f);
-        *reinterpret_cast<bf16x4*>(orow + dt * 32 + 8 * rg + 4 * hi) = y;
-      }
-  } else {
-    float* prow_o = ws_o + (int64_t)myrow * D;
-#pragma unroll
-    for (int dt = 0; dt < DT32; ++dt)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-        *reinterpret_cast<f32x4*>(prow_o + dt * 32 + 8 * rg + 4 * hi) =
-            f32x4{o_acc[dt][rg * 4], o_acc[dt][rg * 4 + 1],
-                  o_acc[dt][rg * 4 + 2], o_acc[dt][rg * 4 + 3]};
-    if (hi == 0) {
-      ws_ml[myrow * 2] = m_run;
-      ws_ml[myrow * 2 + 1] = l_run;
-    }
-  }
-}
-
-// grid B*T*H, D threads: splits combined in index order; dead queries
-// (t >= n, idle slots) are written as exact zeros.
-__global__ void attn_prefill_merge_kernel(
-    const float* __restrict__ ws, bf16* __restrict__ O,
-    const int* __restrict__ lens, const int* __restrict__ n_new, int B, int T,
-    int H, int Hkv, int D, int Smax, int nsplit) {
-  const int bth = blockIdx.x;
-  const int b = bth / (T * H);
-  const int th = bth - b * (T * H);
-  const int t = th / H, h = th - t * H;
-  const int G = H / Hkv, M = T * G;
-  const int hkv = h / G, row = t * G + (h - hkv * G);
-  const int d = threadIdx.x;
-  int L0, n;
-  pf_live(lens, n_new, b, T, Smax, L0, n);
-  bf16* o = O + (int64_t)bth * D + d;
-  if (t >= n) {
-    *o = f2bf(0.f);
-    return;
-  }
-  const int64_t p0 = ((int64_t)b * Hkv + hkv) * nsplit * M + row;
-  const float* po = ws + p0 * D + d;
-  const float* pml = ws + (int64_t)B * Hkv * nsplit * M * D + p0 * 2;
-  float mx = PF_NEG;
-  for (int s = 0; s < nsplit; ++s) mx = fmaxf(mx, pml[(int64_t)s * M * 2]);
-  float num = 0.f, den = 0.f;
-  for (int s = 0; s < nsplit; ++s) {
-    const float w = __expf(pml[(int64_t)s * M * 2] - mx);
-    den += w * pml[(int64_t)s * M * 2 + 1];
-    num += w * po[(int64_t)s * M * D];
-  }
-  *o = f2bf(num / fmaxf(den, 1e-30f));
+  pf_epilogue<D>(o_acc, m_run, l_run, live, O + qo_off, ws_o, ws_ml, myrow,
+                 nsplit, hi);
 }
 
 template <int D, int GSH>
@@ -466,17 +289,11 @@ PRIME_API int prime_attn_prefill_ragged(
     void* ws, const void* lens, const void* n_new, int64_t B, int64_t T,
     int64_t H, int64_t Hkv, int64_t Smax, int64_t D, int64_t split_rows,
     double scale) {
-  if ((D != 64 && D != 128) || B < 1 || T < 1 || H < 1 || Hkv < 1 ||
-      Smax < 1 || T > Smax || H % Hkv != 0 || split_rows < PF_KEY_TILE ||
-      split_rows % PF_KEY_TILE != 0 || !lens || !n_new)
+  if (pf_check_args(B, T, H, Hkv, Smax, D, split_rows, ws, lens, n_new))
     return hipErrorInvalidValue;
   const int64_t G = H / Hkv;
-  if (G != 1 && G != 2 && G != 4 && G != 8) return hipErrorInvalidValue;
   const int64_t nsplit = (Smax + split_rows - 1) / split_rows;
   const int64_t nqt = (T * G + PF_Q_ROWS - 1) / PF_Q_ROWS;
-  if (nsplit > 65535 || B * Hkv > 65535 || B * T * H > 0x7fffffff ||
-      Smax > 0x7fffffff - split_rows - PF_Q_ROWS || (nsplit > 1 && !ws))
-    return hipErrorInvalidValue;
   const int gsh = G == 1 ? 0 : (G == 2 ? 1 : (G == 4 ? 2 : 3));
   const dim3 grid((unsigned)nqt, (unsigned)(B * Hkv), (unsigned)nsplit);
   if (D == 128)

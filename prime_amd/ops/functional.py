@@ -1891,6 +1891,98 @@ def decode_qkv_append_multi_fp8(qkv, cos, sin, cache: KVCacheFp8, pos, n_new,
     return q
 
 
+def attn_prefill_ragged_fp8(q, cache: KVCacheFp8, lens, n_new,
+                            split_rows=None) -> torch.Tensor:
+    """attn_prefill_ragged over an fp8 cache: q [B,T,H,D], the same lens /
+    n_new clamp, dead-query, supported-shape and split_rows rules (and the
+    same workspace); the values attended to are kv_cache_dequant(cache), the
+    chunk's own rows included. No byte and no scale at or beyond L0 + n - 1
+    is read."""
+    _check_fp8_cache(cache, "attn_prefill_ragged_fp8")
+    if q.dim() != 4:
+        raise ValueError("attn_prefill_ragged_fp8 needs q [B,T,H,D]")
+    B, T, H, D = q.shape
+    _, Smax, Hkv, _ = cache.k.shape
+    for name, v in (("lens", lens), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        # the multi-token op's host path has no T limit
+        return attn_decode_ragged_multi_fp8(q, cache, lens, n_new)
+    G = H // Hkv if H % Hkv == 0 else 0
+    if D not in (64, 128) or G not in _RAGGED_GROUPS or not 1 <= T <= Smax:
+        raise NotImplementedError(
+            f"attn_prefill_ragged_fp8 needs head_dim in {{64, 128}}, a GQA "
+            f"group size in {_RAGGED_GROUPS} and 1 <= T <= Smax (got "
+            f"head_dim={D}, heads={H}, kv_heads={Hkv}, T={T}, Smax={Smax})")
+    _fp8_cache_contiguous(cache, "attn_prefill_ragged_fp8")
+    if split_rows is None:
+        split_rows = prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % PREFILL_KEY_TILE != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{PREFILL_KEY_TILE} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    ws = None
+    if nsplit > 1:
+        # the bf16 op's workspace: same shape key, and the ops run in stream order
+        key = (B, Hkv, T * G, D, nsplit, q.device.index)
+        ws = _PREFILL_WS.get(key)
+        if ws is None:
+            ws = _PREFILL_WS[key] = torch.empty(
+                B * Hkv * nsplit * T * G * (D + 2), device=q.device,
+                dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_prefill_ragged_fp8(
+            stream_of(q), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), ptr(o), ptr(ws), ptr(lens),
+            ptr(n_new), B, T, H, Hkv, Smax, D, split_rows, D**-0.5,
+        ),
+        "attn_prefill_ragged_fp8",
+    )
+    return o
+
+
+def prefill_qkv_append_fp8(qkv, cos, sin, cache: KVCacheFp8, pos, n_new,
+                           n_heads: int, n_kv_heads: int) -> torch.Tensor:
+    """decode_qkv_append_multi_fp8 for a prefill chunk of any length: the same
+    dead-token rule, rotated q [B,T,H,D] (bit-identical to prefill_qkv_append)
+    and per-row quantisation (bytes and scales equal decode_qkv_append_fp8's
+    for the same row)."""
+    _check_fp8_cache(cache, "prefill_qkv_append_fp8")
+    H, Hkv = n_heads, n_kv_heads
+    _, Smax, Hkv_c, D = cache.k.shape
+    R = cos.shape[0]
+    if qkv.dim() != 3 or qkv.shape[2] != (H + 2 * Hkv) * D or Hkv_c != Hkv:
+        raise ValueError(f"prefill_qkv_append_fp8: qkv {tuple(qkv.shape)} does "
+                         f"not match heads={H}, kv_heads={Hkv}, head_dim={D}")
+    B, T = qkv.shape[:2]
+    for name, v in (("pos", pos), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != qkv.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on qkv's device")
+    if not _is_hip(qkv):
+        # the multi-token op's host path has no T limit
+        return decode_qkv_append_multi_fp8(qkv, cos, sin, cache, pos, n_new,
+                                           n_heads, n_kv_heads)
+    if D not in (64, 128) or T < 1:
+        raise NotImplementedError(
+            f"prefill_qkv_append_fp8 needs head_dim in {{64, 128}} and T >= 1 "
+            f"(got head_dim={D}, T={T})")
+    _fp8_cache_contiguous(cache, "prefill_qkv_append_fp8")
+    qkv = qkv.contiguous()
+    q = torch.empty(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_prefill_qkv_append_fp8(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cache.k_scale), ptr(cache.v_scale), ptr(cos), ptr(sin),
+            ptr(pos), ptr(n_new), B, T, H, Hkv, D, Smax, R,
+        ),
+        "prefill_qkv_append_fp8",
+    )
+    return q
+
+
 def mfma_probe32(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     """32x32x16 bf16 MFMA single-tile matmul (layout verification)."""
     C = torch.empty(32, 32, device=A.device, dtype=torch.float32)

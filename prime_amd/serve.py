@@ -64,10 +64,9 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
     if kv_dtype not in gen_mod.KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {gen_mod.KV_DTYPES} (got "
                          f"{kv_dtype!r})")
-    if prefill_chunk < 0 or prefill_chunk % 8 != 0 or \
-            (prefill_chunk and kv_dtype != "bf16"):
-        raise ValueError("prefill_chunk must be 0 or a positive multiple of 8, "
-                         "and needs kv_dtype='bf16'")
+    # with kv_dtype "fp8" generate_batch decides (a model on the GPU)
+    if prefill_chunk < 0 or prefill_chunk % 8 != 0:
+        raise ValueError("prefill_chunk must be 0 or a positive multiple of 8")
     app = FastAPI(title="prime-amd inference")
     dev = next(model.parameters()).device
     pending: queue.Queue = queue.Queue()
