@@ -694,6 +694,18 @@ def _kv_dtype_option(value: str) -> str:
     return value
 
 
+def _kv_layout_option(value: str) -> str:
+    from ..models.generate import KV_LAYOUTS
+
+    if value not in KV_LAYOUTS:
+        raise typer.BadParameter(f"choose from {', '.join(KV_LAYOUTS)}")
+    return value
+
+
+_KV_LAYOUT_HELP = ("KV cache layout of the ragged decode path: contiguous (one "
+                   "slab per sequence), or paged (a pool of fixed-size pages "
+                   "and a block table; bf16 cache, no lookahead)")
+
 _KV_DTYPE_HELP = ("KV cache storage of the ragged decode path: bf16, or fp8 "
                   "(e4m3 bytes + one fp32 scale per row and kv head, half "
                   "the memory)")
@@ -724,6 +736,14 @@ def generate_cmd(
         "chunked ragged prefill: feed the prompts to the cache in steps of "
         "this many tokens (a multiple of 8, bf16 or fp8 cache; runs as a "
         "ragged batch) instead of one prefill padded to the longest prompt")),
+    kv_layout: str = typer.Option("contiguous", "--kv-layout",
+                                  callback=_kv_layout_option,
+                                  help=_KV_LAYOUT_HELP),
+    page_size: int = typer.Option(64, "--page-size", help=(
+        "rows per page of the paged KV cache: 64, 128 or 256")),
+    kv_pages: Optional[int] = typer.Option(None, "--kv-pages", help=(
+        "pages in the paged KV pool per layer (default: the contiguous "
+        "cache's capacity)")),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch
@@ -762,7 +782,8 @@ def generate_cmd(
     else:
         groups = [g for pt in prompt_tokens for g in pt.split(";") if g.strip()]
         prompts = [[int(t) for t in g.split(",")] for g in groups]
-    if len(prompts) > 1 or kv_dtype != "bf16" or lookahead or prefill_chunk:
+    if len(prompts) > 1 or kv_dtype != "bf16" or lookahead or prefill_chunk \
+            or kv_layout != "contiguous":
         # several prompts of different lengths: one ragged batch, one output
         # line (prompt + new tokens) per prompt; the fp8 cache and lookahead
         # decoding exist on the ragged path only, so they take a single
@@ -771,7 +792,9 @@ def generate_cmd(
 
         outs = generate_batch(m, prompts, max_new, temperature=temperature,
                               top_k=top_k, seed=seed, kv_dtype=kv_dtype,
-                              lookahead=lookahead, prefill_chunk=prefill_chunk)
+                              lookahead=lookahead, prefill_chunk=prefill_chunk,
+                              kv_layout=kv_layout, page_size=page_size,
+                              kv_pages=kv_pages)
         for p_ids, new in zip(prompts, outs):
             if tok is not None:
                 from ..utils.tokenizer import decode as tok_decode
@@ -932,6 +955,14 @@ def serve_cmd(
                                           "waiting request waits for company"),
     kv_dtype: str = typer.Option("bf16", "--kv-dtype", callback=_kv_dtype_option,
                                  help=_KV_DTYPE_HELP),
+    kv_layout: str = typer.Option("contiguous", "--kv-layout",
+                                  callback=_kv_layout_option,
+                                  help=_KV_LAYOUT_HELP),
+    page_size: int = typer.Option(64, "--page-size", help=(
+        "rows per page of the paged KV cache: 64, 128 or 256")),
+    kv_pages: Optional[int] = typer.Option(None, "--kv-pages", help=(
+        "pages in the paged KV pool per layer (default: the contiguous "
+        "cache's capacity)")),
 ):
     """Serve the model over an OpenAI-style HTTP API (engine-side
     counterpart of the reference's hosted inference surface):
@@ -952,7 +983,9 @@ def serve_cmd(
         raise typer.Exit(1)
     secho(f"serving {model} on http://{host}:{port} (ctrl-c to stop)", fg="green")
     uvicorn.run(create_app(m, model, tok, max_batch=max_batch,
-                           batch_window_ms=batch_window_ms, kv_dtype=kv_dtype),
+                           batch_window_ms=batch_window_ms, kv_dtype=kv_dtype,
+                           kv_layout=kv_layout, page_size=page_size,
+                           kv_pages=kv_pages),
                 host=host, port=port,
                 log_level="warning")
 

@@ -18,6 +18,7 @@ from .. import ops
 from .llama import Llama
 
 KV_DTYPES = ("bf16", "fp8")
+KV_LAYOUTS = ("contiguous", "paged")
 
 
 def _pad64(n: int) -> int:
@@ -182,6 +183,9 @@ def generate_batch(
     kv_dtype: str = "bf16",
     lookahead: int = 0,
     prefill_chunk: int = 0,
+    kv_layout: str = "contiguous",
+    page_size: int = 64,
+    kv_pages: int | None = None,
 ) -> list[list[int]]:
     """Ragged batched generation: `prompts` is a list of token-id lists of
     different lengths; returns the NEW tokens of each. max_new_tokens,
@@ -225,7 +229,20 @@ def generate_batch(
     its own length, not the longest one's. Runs eagerly. Over an fp8 cache a
     chunk attends to the QUANTISED rows, its own included, so the first new
     token is that of the quantised cache, not that of the bf16 cache as with
-    the padded prefill."""
+    the padded prefill.
+
+    kv_layout "paged" (bf16 cache, no lookahead) stores the cache as a pool of
+    kv_pages pages of page_size rows (64, 128 or 256) per layer plus one
+    block table shared by the layers (ops.KVCachePaged). kv_pages defaults to
+    the contiguous cache's capacity, Bk * smax / page_size. A host-side free
+    list hands every sequence ceil((prompt + max_new) / page_size) pages at
+    the start of the call and takes them back when it ends; a batch that
+    needs more pages than the pool has raises ValueError before any work. A
+    short prompt next to a long one then costs its own pages, not a slab of
+    the longest length. The prompts always enter through the chunked ragged
+    prefill (prefill_chunk, or 256 tokens a step); the decode graph reads the
+    table from a stable device buffer, and its session key carries the
+    layout, the page size and the pool size."""
     lookahead = int(lookahead)
     prefill_chunk = int(prefill_chunk)
     if prefill_chunk < 0 or prefill_chunk % 8 != 0:
@@ -236,6 +253,20 @@ def generate_batch(
     if kv_dtype not in KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got "
                          f"{kv_dtype!r})")
+    if kv_layout not in KV_LAYOUTS:
+        raise ValueError(f"kv_layout must be one of {KV_LAYOUTS} (got "
+                         f"{kv_layout!r})")
+    paged = kv_layout == "paged"
+    if paged:
+        if kv_dtype != "bf16" or lookahead:
+            raise ValueError("kv_layout='paged' stores a bf16 cache and "
+                             "decodes one token per step: it cannot be "
+                             "combined with kv_dtype='fp8' or lookahead > 0")
+        if page_size not in ops.KV_PAGE_SIZES:
+            raise ValueError(f"page_size must be one of {ops.KV_PAGE_SIZES} "
+                             f"(got {page_size})")
+        if kv_pages is not None and int(kv_pages) < 1:
+            raise ValueError(f"kv_pages must be positive (got {kv_pages})")
     model.eval()
     cfg = model.cfg
     p0 = next(model.parameters())
@@ -276,14 +307,34 @@ def generate_batch(
     # launch the same kernels on the same shapes and agree exactly
     smax = min(_pad64(cfg.max_seq), _pad64(max(total, 1024))) if on_gpu \
         else _pad64(total)
+    if paged:
+        P = page_size
+        smax = -(-smax // P) * P  # whole pages
+        n_pool = int(kv_pages) if kv_pages is not None else Bk * smax // P
+        need = [-(-(L0[b] + max(max_new[b], 0)) // P) for b in range(n)]
+        if sum(need) > n_pool:
+            raise ValueError(f"the batch needs {sum(need)} KV pages of "
+                             f"{P} rows, the pool has {n_pool}")
     sessions = getattr(model, "_decode_sessions", None)
     if sessions is None:
         sessions = model._decode_sessions = {}
     key = ("ragged", Bk, smax, dev.index, kv_dtype) if not lookahead \
         else ("ragged_multi", Bk, smax, dev.index, lookahead + 1, kv_dtype)
+    if paged:
+        key = ("ragged_paged", Bk, smax, dev.index, P, n_pool)
     sess = sessions.get(key) if graphing else None
     if sess is None:
-        if kv_dtype == "fp8":
+        if paged:
+            # one table for all layers; its pointer is what the graph reads
+            table = torch.full((Bk, smax // P), -1, dtype=torch.int32,
+                               device=dev)
+            caches = [ops.KVCachePaged(
+                torch.zeros(n_pool, P, cfg.n_kv_heads, cfg.head_dim,
+                            device=dev, dtype=dtype),
+                torch.zeros(n_pool, P, cfg.n_kv_heads, cfg.head_dim,
+                            device=dev, dtype=dtype), table)
+                for _ in range(cfg.n_layers)]
+        elif kv_dtype == "fp8":
             caches = [ops.kv_cache_fp8(Bk, smax, cfg.n_kv_heads, cfg.head_dim, dev)
                       for _ in range(cfg.n_layers)]
         else:
@@ -295,6 +346,8 @@ def generate_batch(
                 for _ in range(cfg.n_layers)
             ]
         sess = _ragged_state(caches, Bk, dev)
+        if paged:
+            sess["pages"] = ops.KVPageAllocator(n_pool)
         if lookahead:
             sess["tok"] = torch.zeros(Bk, lookahead + 1, dtype=torch.int64,
                                       device=dev)
@@ -306,6 +359,34 @@ def generate_batch(
                             else _ragged_step)
             sessions[key] = sess
     caches = sess["caches"]
+    if paged:
+        # the call's pages; handed back (and the table cleared) when it ends
+        held = [sess["pages"].alloc(need[b]) for b in range(n)]
+        rows = torch.full(tuple(caches[0].table.shape), -1, dtype=torch.int32)
+        for b in range(n):
+            rows[b, :need[b]] = torch.tensor(held[b], dtype=torch.int32)
+        caches[0].table.copy_(rows)
+        try:
+            return _generate_ragged(model, sess, prompts, max_new, temps,
+                                    topks, seeds, stops, out, done, graphing,
+                                    0, prefill_chunk or 256)
+        finally:
+            for ids in held:
+                sess["pages"].free(ids)
+            caches[0].table.fill_(-1)
+    return _generate_ragged(model, sess, prompts, max_new, temps, topks, seeds,
+                            stops, out, done, graphing, lookahead,
+                            prefill_chunk)
+
+
+def _generate_ragged(model, sess, prompts, max_new, temps, topks, seeds, stops,
+                     out, done, graphing, lookahead, prefill_chunk):
+    """Prefill and decode loop of generate_batch over the session's caches
+    (any layout); fills `out` and returns it."""
+    caches = sess["caches"]
+    n, Bk = len(prompts), sess["pos"].shape[0]
+    L0 = [len(p) for p in prompts]
+    dev = sess["pos"].device
     gens = []
     for b in range(n):
         g = torch.Generator(device="cpu")
@@ -389,7 +470,8 @@ def generate_batch(
 def prefill_chunked(model, caches, prompts, chunk: int) -> torch.Tensor:
     """Chunked ragged prefill: write `prompts` (token-id lists of different
     lengths) into the first len(prompts) slots of `caches` [(k, v) or an
-    ops.KVCacheFp8 per layer, each k [Bk,Smax,Hkv,D]] in steps of `chunk`
+    ops.KVCacheFp8 per layer, each k [Bk,Smax,Hkv,D]; or an ops.KVCachePaged
+    per layer, whose table rows are the slots] in steps of `chunk`
     tokens and return the hidden state at each prompt's last token,
     [len(prompts), dim]. At every step slot b takes min(chunk, remaining_b)
     tokens at pos = done_b with lens = done_b + 1; finished and padding slots
@@ -397,8 +479,11 @@ def prefill_chunked(model, caches, prompts, chunk: int) -> torch.Tensor:
     attends to the quantised rows, its own included: the result is that of
     the quantised cache, not of the unquantised k and v as with the padded
     prefill."""
-    dev = caches[0][0].device  # k of a (k, v) pair or of a KVCacheFp8
-    Bk, n = caches[0][0].shape[0], len(prompts)
+    dev = caches[0][0].device  # k of a (k, v) pair, KVCacheFp8 or KVCachePaged
+    # slots: a paged cache's k is the pool, its table has one row per slot
+    Bk = caches[0].table.shape[0] if isinstance(caches[0], ops.KVCachePaged) \
+        else caches[0][0].shape[0]
+    n = len(prompts)
     L = [len(p) for p in prompts]
     last = [None] * n
     for done in range(0, max(L), chunk):

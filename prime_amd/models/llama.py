@@ -72,6 +72,15 @@ class Attention(nn.Module):
             # a chunk the verification kernels do not take (T > 8 or more
             # than 64 query rows per kv head) is a prefill chunk
             chunk = S > 8 or S * (cfg.n_heads // cfg.n_kv_heads) > 64
+            if isinstance(cache, ops.KVCachePaged):
+                # a paged cache has no verification kernels: every T is a
+                # prefill chunk
+                q = ops.prefill_qkv_append_paged(
+                    self.wqkv(x), cos, sin, cache, seq_pos["pos"],
+                    seq_pos["n_new"], cfg.n_heads, cfg.n_kv_heads)
+                o = ops.attn_prefill_ragged_paged(
+                    q, cache, seq_pos["lens"], seq_pos["n_new"])
+                return self.wo(o.reshape(B, S, cfg.n_heads * hd))
             if isinstance(cache, ops.KVCacheFp8):
                 # pinned by test_decode_multi_cpu.py::test_model_guards
                 if not cache.k.is_cuda:
@@ -118,6 +127,12 @@ class Attention(nn.Module):
                 raise ValueError("seq_pos cannot be combined with doc_start, "
                                  "pos_dev or sequence parallelism")
             qkv = self.wqkv(x).view(B, -1)
+            if isinstance(cache, ops.KVCachePaged):
+                q = ops.decode_qkv_append_paged(qkv, cos, sin, cache,
+                                                seq_pos["pos"], cfg.n_heads,
+                                                cfg.n_kv_heads)
+                o = ops.attn_decode_ragged_paged(q, cache, seq_pos["lens"])
+                return self.wo(o.reshape(B, 1, cfg.n_heads * hd))
             if isinstance(cache, ops.KVCacheFp8):
                 q = ops.decode_qkv_append_fp8(qkv, cos, sin, cache,
                                               seq_pos["pos"], cfg.n_heads,
@@ -151,6 +166,10 @@ class Attention(nn.Module):
                 o = ops.flash_attention(q, k, v, causal=True,
                                         doc_start=doc_start)
             return self.wo(o.reshape(B, S, cfg.n_heads * hd))
+        if isinstance(cache, ops.KVCachePaged):
+            raise ValueError("a paged KV cache is written and read through "
+                             "the ragged kernels only (seq_pos): use "
+                             "generate_batch(kv_layout='paged')")
         fp8_cache = isinstance(cache, ops.KVCacheFp8)
         if fp8_cache and (S == 1 or pos_dev is not None):
             # the single-position decode paths run the older one-length

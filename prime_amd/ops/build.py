@@ -19,7 +19,9 @@ ARCH = os.environ.get("PRIME_AMD_ARCH", "gfx950")
 # sources compiled on their own, without the packed fp32 VALU instructions
 # (v_pk_add/mul/fma_f32); new kernel files go here
 NO_PACKED_FP32 = ("decode_multi.hip", "decode_multi_fp8.hip",
-                  "prefill_ragged.hip", "prefill_ragged_fp8.hip")
+                  "prefill_ragged.hip", "prefill_ragged_fp8.hip",
+                  "decode_ragged_paged.hip", "prefill_ragged_paged.hip",
+                  "append_paged.hip")
 _NO_PACKED_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

@@ -1983,6 +1983,301 @@ def prefill_qkv_append_fp8(qkv, cos, sin, cache: KVCacheFp8, pos, n_new,
     return q
 
 
+# ---------------------------------------------------------- paged KV cache
+KV_PAGE_SIZES = (64, 128, 256)
+
+
+class KVCachePaged(NamedTuple):
+    """One layer's paged bf16 KV cache. k, v: the pools [n_pages, P, Hkv, D],
+    contiguous, P in KV_PAGE_SIZES; table: int32 [B, max_pages] on the pools'
+    device (it may be shared by all layers), read inside the kernels. Logical
+    row r of sequence b is pool row table[b, r // P] * P + r % P; the logical
+    capacity Smax = max_pages * P takes the place of the contiguous cache's
+    Smax. Readers clamp the entries they use to [0, n_pages) and never read
+    the entry of a page without a live row; writers treat a token whose entry
+    is outside [0, n_pages) as dead. Two table rows may name the same page:
+    read-only prefix sharing needs nothing from the readers."""
+    k: torch.Tensor
+    v: torch.Tensor
+    table: torch.Tensor
+
+
+def kv_cache_paged(n_pages: int, P: int, B: int, max_pages: int, Hkv: int,
+                   D: int, device=None, dtype=torch.bfloat16) -> KVCachePaged:
+    """A zeroed paged KV cache for one layer; every table entry is -1."""
+    if P not in KV_PAGE_SIZES:
+        raise ValueError(f"page size must be one of {KV_PAGE_SIZES} (got {P})")
+    return KVCachePaged(
+        torch.zeros(n_pages, P, Hkv, D, device=device, dtype=dtype),
+        torch.zeros(n_pages, P, Hkv, D, device=device, dtype=dtype),
+        torch.full((B, max_pages), -1, device=device, dtype=torch.int32))
+
+
+def _check_paged(cache, what: str):
+    """(n_pages, P, Hkv, D, B, max_pages) of a well-formed KVCachePaged."""
+    if not isinstance(cache, KVCachePaged):
+        raise TypeError(f"{what} needs a KVCachePaged (got "
+                        f"{type(cache).__name__})")
+    k, v, table = cache
+    if table is None:
+        raise ValueError(f"{what}: KVCachePaged without a block table")
+    if k.dim() != 4 or v.shape != k.shape or v.dtype != k.dtype \
+            or table.dim() != 2 or table.dtype != torch.int32 \
+            or table.device != k.device or v.device != k.device:
+        raise ValueError(f"{what}: KVCachePaged needs pools k, v [n_pages, P, "
+                         f"Hkv, D] and an int32 table [B, max_pages] on one "
+                         f"device")
+    if k.shape[1] not in KV_PAGE_SIZES:
+        raise NotImplementedError(f"{what}: page size must be one of "
+                                  f"{KV_PAGE_SIZES} (got {k.shape[1]})")
+    if not (k.is_contiguous() and v.is_contiguous() and table.is_contiguous()):
+        raise ValueError(f"{what} needs contiguous pools and table")
+    return (*k.shape, *table.shape)
+
+
+def kv_paged_gather(cache: KVCachePaged):
+    """The rows a paged cache holds, as contiguous (k, v) [B, Smax, Hkv, D]
+    with Smax = max_pages * P and zeros where the table entry is outside
+    [0, n_pages): the executable definition of the layout."""
+    n_pages, P, Hkv, D, B, mp = _check_paged(cache, "kv_paged_gather")
+    ok = ((cache.table >= 0) & (cache.table < n_pages))[..., None, None, None]
+    idx = cache.table.clamp(0, n_pages - 1).long()
+
+    def g(pool):
+        return torch.where(ok, pool[idx], torch.zeros((), dtype=pool.dtype,
+                                                      device=pool.device)
+                           ).reshape(B, mp * P, Hkv, D)
+
+    return g(cache.k), g(cache.v)
+
+
+def attn_decode_ragged_paged(q, cache: KVCachePaged, lens,
+                             split_rows=None) -> torch.Tensor:
+    """attn_decode_ragged over a paged cache: q [B,H,D] (or [B,1,H,D]);
+    sequence b attends to its logical rows [0, lens[b]), with `lens` clamped
+    to [0, Smax = max_pages * P] at kernel time; an idle slot (lens[b] == 0)
+    gives exact zeros. Same splits (decode_ragged_split over Smax), workspace
+    and index-order merge as attn_decode_ragged, and the same bits for the
+    same rows. The table is read in the kernel (a captured graph replays
+    while its contents change): only entries of pages with a row below
+    lens[b] are used, clamped to [0, n_pages)."""
+    if q.dim() == 4:
+        q = q.squeeze(1)
+    n_pages, P, Hkv, D_c, B_t, mp = _check_paged(cache, "attn_decode_ragged_paged")
+    B, H, D = q.shape
+    Smax = mp * P
+    if B_t != B or D_c != D or cache.k.dtype != q.dtype:
+        raise ValueError(f"attn_decode_ragged_paged: q {tuple(q.shape)} does not "
+                         f"match pools {tuple(cache.k.shape)} / table "
+                         f"{tuple(cache.table.shape)}")
+    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != q.device:
+        raise ValueError("lens must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        return attn_decode_ragged(q, *kv_paged_gather(cache), lens)
+    _check_ragged_shape(H, Hkv, D)
+    if split_rows is None:
+        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % DECODE_RAGGED_CHUNK != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{DECODE_RAGGED_CHUNK} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    G = H // Hkv
+    key = (B, Hkv, G, D, nsplit, q.device.index)  # the sibling's workspace
+    ws = _RAGGED_WS.get(key)
+    if ws is None:
+        ws = _RAGGED_WS[key] = torch.empty(
+            B * Hkv, nsplit, G * (D + 2), device=q.device, dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_decode_ragged_paged(
+            stream_of(q), ptr(q), ptr(cache.k), ptr(cache.v), ptr(o), ptr(ws),
+            ptr(lens), ptr(cache.table), B, H, Hkv, P, n_pages, mp, D,
+            split_rows, D**-0.5,
+        ),
+        "attn_decode_ragged_paged",
+    )
+    return o
+
+
+def attn_prefill_ragged_paged(q, cache: KVCachePaged, lens, n_new,
+                              split_rows=None) -> torch.Tensor:
+    """attn_prefill_ragged over a paged cache: q [B,T,H,D] against logical
+    rows that already hold the new tokens. Same (lens, n_new) clamp with
+    Smax = max_pages * P, same dead rows (exact zeros), splits
+    (prefill_ragged_split over Smax) and merge, and the same bits for the
+    same rows; 1 <= T <= Smax. Only table entries of pages with a row below
+    L0 + n - 1 are used, clamped to [0, n_pages)."""
+    n_pages, P, Hkv, D_c, B_t, mp = _check_paged(cache, "attn_prefill_ragged_paged")
+    if q.dim() != 4:
+        raise ValueError("attn_prefill_ragged_paged needs q [B,T,H,D]")
+    B, T, H, D = q.shape
+    Smax = mp * P
+    if B_t != B or D_c != D or cache.k.dtype != q.dtype:
+        raise ValueError(f"attn_prefill_ragged_paged: q {tuple(q.shape)} does "
+                         f"not match pools {tuple(cache.k.shape)} / table "
+                         f"{tuple(cache.table.shape)}")
+    for name, v in (("lens", lens), ("n_new", n_new)):
+        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    if not _is_hip(q):
+        return attn_prefill_ragged(q, *kv_paged_gather(cache), lens, n_new)
+    G = H // Hkv if H % Hkv == 0 else 0
+    if D not in (64, 128) or G not in _RAGGED_GROUPS or not 1 <= T <= Smax:
+        raise NotImplementedError(
+            f"attn_prefill_ragged_paged needs head_dim in {{64, 128}}, a GQA "
+            f"group size in {_RAGGED_GROUPS} and 1 <= T <= Smax (got "
+            f"head_dim={D}, heads={H}, kv_heads={Hkv}, T={T}, Smax={Smax})")
+    if split_rows is None:
+        split_rows = prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device))
+    if split_rows <= 0 or split_rows % PREFILL_KEY_TILE != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{PREFILL_KEY_TILE} (got {split_rows})")
+    nsplit = -(-Smax // split_rows)
+    ws = None
+    if nsplit > 1:
+        key = (B, Hkv, T * G, D, nsplit, q.device.index)  # the sibling's
+        ws = _PREFILL_WS.get(key)
+        if ws is None:
+            ws = _PREFILL_WS[key] = torch.empty(
+                B * Hkv * nsplit * T * G * (D + 2), device=q.device,
+                dtype=torch.float32)
+    q = q.contiguous()
+    o = torch.empty_like(q)
+    check(
+        lib().prime_attn_prefill_ragged_paged(
+            stream_of(q), ptr(q), ptr(cache.k), ptr(cache.v), ptr(o), ptr(ws),
+            ptr(lens), ptr(n_new), ptr(cache.table), B, T, H, Hkv, P, n_pages,
+            mp, D, split_rows, D**-0.5,
+        ),
+        "attn_prefill_ragged_paged",
+    )
+    return o
+
+
+def _append_paged_host(x, cos, sin, cache, pos, n_new, H, Hkv):
+    """Host path of both paged appends: x [B,T,H+2Hkv,D]; the contiguous host
+    paths' per-token pass with the destination row taken through the table."""
+    n_pages, P = cache.k.shape[:2]
+    B, T = x.shape[:2]
+    lim = min(cache.table.shape[1] * P, cos.shape[0])
+    q = torch.zeros(B, T, H, x.shape[3], dtype=x.dtype, device=x.device)
+    table = cache.table.tolist()
+    for b, (p0, n) in enumerate(zip(pos.tolist(), n_new)):
+        for t in range(T):
+            p = p0 + t
+            if p0 < 0 or t >= n or p >= lim:
+                continue
+            e = table[b][p // P]
+            if not 0 <= e < n_pages:
+                continue
+            xt = x[b:b + 1, t:t + 1]
+            q[b, t] = ref.apply_rope(xt[:, :, :H], cos, sin, p)[0, 0]
+            cache.k[e, p % P] = ref.apply_rope(xt[:, :, H:H + Hkv], cos, sin, p)[0, 0]
+            cache.v[e, p % P] = x[b, t, H + Hkv:]
+    return q
+
+
+def _check_append_paged(qkv, cache, vecs, H, Hkv, what: str):
+    n_pages, P, Hkv_c, D, B_t, mp = _check_paged(cache, what)
+    if qkv.shape[-1] != (H + 2 * Hkv) * D or Hkv_c != Hkv \
+            or qkv.shape[0] != B_t or cache.k.dtype != qkv.dtype:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} does not match "
+                         f"heads={H}, kv_heads={Hkv}, head_dim={D}, table "
+                         f"{tuple(cache.table.shape)}")
+    for name, v in vecs:
+        if v.dtype != torch.int32 or v.shape != (B_t,) or v.device != qkv.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on qkv's device")
+    if _is_hip(qkv) and D not in (64, 128):
+        raise NotImplementedError(
+            f"{what} needs head_dim in {{64, 128}} (got {D})")
+    return n_pages, P, D, mp
+
+
+def decode_qkv_append_paged(qkv, cos, sin, cache: KVCachePaged, pos,
+                            n_heads: int, n_kv_heads: int) -> torch.Tensor:
+    """decode_qkv_append into a paged cache: qkv [B, (H+2Hkv)*D], one token
+    per sequence; q and the k, v rows written are bit-identical to
+    decode_qkv_append's, the row being table[b, pos[b] // P] * P + pos[b] % P.
+    A slot is idle (nothing written, zero q) if pos[b] < 0, pos[b] >=
+    min(Smax, len(cos)), or its table entry is outside [0, n_pages): an
+    invalid entry is never clamped for a write."""
+    H, Hkv = n_heads, n_kv_heads
+    if qkv.dim() != 2:
+        raise ValueError("decode_qkv_append_paged needs qkv [B, (H+2Hkv)*D]")
+    n_pages, P, D, mp = _check_append_paged(
+        qkv, cache, (("pos", pos),), H, Hkv, "decode_qkv_append_paged")
+    B = qkv.shape[0]
+    if not _is_hip(qkv):
+        return _append_paged_host(qkv.view(B, 1, H + 2 * Hkv, D), cos, sin,
+                                  cache, pos, [1] * B, H, Hkv)[:, 0]
+    qkv = qkv.contiguous()
+    q = torch.empty(B, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_decode_qkv_append_paged(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cos), ptr(sin), ptr(pos), ptr(cache.table), B, H, Hkv, D, P,
+            n_pages, mp, cos.shape[0],
+        ),
+        "decode_qkv_append_paged",
+    )
+    return q
+
+
+def prefill_qkv_append_paged(qkv, cos, sin, cache: KVCachePaged, pos, n_new,
+                             n_heads: int, n_kv_heads: int) -> torch.Tensor:
+    """prefill_qkv_append into a paged cache: qkv [B,T,(H+2Hkv)*D], any T;
+    token t of slot b is rotated at p = pos[b] + t and its k, v go to pool
+    row table[b, p // P] * P + p % P (bit-identical to prefill_qkv_append).
+    A token is dead (nothing written, zero q rows) if pos[b] < 0, t >=
+    n_new[b], p >= min(Smax, len(cos)), or its table entry is outside
+    [0, n_pages)."""
+    H, Hkv = n_heads, n_kv_heads
+    if qkv.dim() != 3 or qkv.shape[1] < 1:
+        raise ValueError("prefill_qkv_append_paged needs qkv [B,T,(H+2Hkv)*D]")
+    n_pages, P, D, mp = _check_append_paged(
+        qkv, cache, (("pos", pos), ("n_new", n_new)), H, Hkv,
+        "prefill_qkv_append_paged")
+    B, T = qkv.shape[:2]
+    if not _is_hip(qkv):
+        return _append_paged_host(qkv.view(B, T, H + 2 * Hkv, D), cos, sin,
+                                  cache, pos, n_new.tolist(), H, Hkv)
+    qkv = qkv.contiguous()
+    q = torch.empty(B, T, H, D, dtype=qkv.dtype, device=qkv.device)
+    check(
+        lib().prime_prefill_qkv_append_paged(
+            stream_of(qkv), ptr(qkv), ptr(q), ptr(cache.k), ptr(cache.v),
+            ptr(cos), ptr(sin), ptr(pos), ptr(n_new), ptr(cache.table), B, T,
+            H, Hkv, D, P, n_pages, mp, cos.shape[0],
+        ),
+        "prefill_qkv_append_paged",
+    )
+    return q
+
+
+class KVPageAllocator:
+    """Host-side free list over the pages of a pool: alloc(n) hands out n
+    distinct page ids (ValueError when fewer are free), free(ids) returns
+    them."""
+
+    def __init__(self, n_pages: int):
+        self.n_pages = int(n_pages)
+        self._free = list(range(self.n_pages - 1, -1, -1))
+
+    @property
+    def n_free(self) -> int:
+        return len(self._free)
+
+    def alloc(self, n: int) -> list:
+        if n > len(self._free):
+            raise ValueError(f"KV page pool exhausted: {n} pages wanted, "
+                             f"{len(self._free)} of {self.n_pages} free")
+        return [self._free.pop() for _ in range(n)]
+
+    def free(self, ids) -> None:
+        self._free.extend(reversed(list(ids)))
+
+
 def mfma_probe32(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     """32x32x16 bf16 MFMA single-tile matmul (layout verification)."""
     C = torch.empty(32, 32, device=A.device, dtype=torch.float32)

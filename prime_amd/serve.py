@@ -54,7 +54,8 @@ class ChatRequest(BaseModel):
 
 def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                batch_window_ms: float = 5.0, kv_dtype: str = "bf16",
-               prefill_chunk: int = 0):
+               prefill_chunk: int = 0, kv_layout: str = "contiguous",
+               page_size: int = 64, kv_pages: Optional[int] = None):
     from fastapi import FastAPI, HTTPException
 
     from .models import generate as gen_mod
@@ -64,6 +65,11 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
     if kv_dtype not in gen_mod.KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {gen_mod.KV_DTYPES} (got "
                          f"{kv_dtype!r})")
+    if kv_layout not in gen_mod.KV_LAYOUTS:
+        raise ValueError(f"kv_layout must be one of {gen_mod.KV_LAYOUTS} (got "
+                         f"{kv_layout!r})")
+    if kv_layout == "paged" and kv_dtype != "bf16":
+        raise ValueError("kv_layout='paged' stores a bf16 cache")
     # with kv_dtype "fp8" generate_batch decides (a model on the GPU)
     if prefill_chunk < 0 or prefill_chunk % 8 != 0:
         raise ValueError("prefill_chunk must be 0 or a positive multiple of 8")
@@ -90,7 +96,8 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                     top_k=[r.top_k for _, r, _ in items],
                     seed=[r.seed for _, r, _ in items],
                     stop_token_ids=list(stop), kv_dtype=kv_dtype,
-                    prefill_chunk=prefill_chunk)
+                    prefill_chunk=prefill_chunk, kv_layout=kv_layout,
+                    page_size=page_size, kv_pages=kv_pages)
                 for (_, _, fut), new in zip(items, outs):
                     fut.set_result(new)
             except Exception as e:  # noqa: BLE001 - reported to every caller
@@ -173,7 +180,7 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
     @app.get("/health")
     def health():
         return {"status": "ok", "model": model_name, "device": str(dev),
-                "kv_dtype": kv_dtype}
+                "kv_dtype": kv_dtype, "kv_layout": kv_layout}
 
     @app.get("/v1/models")
     def models():
