@@ -694,6 +694,14 @@ def _kv_dtype_option(value: str) -> str:
     return value
 
 
+def _weight_dtype_option(value: str) -> str:
+    from ..models.generate import WEIGHT_DTYPES
+
+    if value not in WEIGHT_DTYPES:
+        raise typer.BadParameter(f"choose from {', '.join(WEIGHT_DTYPES)}")
+    return value
+
+
 def _kv_layout_option(value: str) -> str:
     from ..models.generate import KV_LAYOUTS
 
@@ -709,6 +717,11 @@ _KV_LAYOUT_HELP = ("KV cache layout of the ragged decode path: contiguous (one "
 _KV_DTYPE_HELP = ("KV cache storage of the ragged decode path: bf16, or fp8 "
                   "(e4m3 bytes + one fp32 scale per row and kv head, half "
                   "the memory)")
+
+
+_WEIGHT_DTYPE_HELP = ("weights read by the decode steps of the ragged path: "
+                      "bf16, or fp8 (an e4m3 copy with one scale per output "
+                      "channel, half the weight traffic; needs a GPU)")
 
 
 # --------------------------------------------------------------- generate
@@ -744,6 +757,11 @@ def generate_cmd(
     kv_pages: Optional[int] = typer.Option(None, "--kv-pages", help=(
         "pages in the paged KV pool per layer (default: the contiguous "
         "cache's capacity)")),
+    weight_dtype: str = typer.Option("bf16", "--weight-dtype",
+                                     callback=_weight_dtype_option,
+                                     help=_WEIGHT_DTYPE_HELP + "; with fp8 a "
+                                     "single prompt runs as a ragged batch of "
+                                     "one"),
 ):
     """Generate tokens with the KV-cache decode path (greedy by default)."""
     import torch
@@ -783,7 +801,7 @@ def generate_cmd(
         groups = [g for pt in prompt_tokens for g in pt.split(";") if g.strip()]
         prompts = [[int(t) for t in g.split(",")] for g in groups]
     if len(prompts) > 1 or kv_dtype != "bf16" or lookahead or prefill_chunk \
-            or kv_layout != "contiguous":
+            or kv_layout != "contiguous" or weight_dtype != "bf16":
         # several prompts of different lengths: one ragged batch, one output
         # line (prompt + new tokens) per prompt; the fp8 cache and lookahead
         # decoding exist on the ragged path only, so they take a single
@@ -794,7 +812,7 @@ def generate_cmd(
                               top_k=top_k, seed=seed, kv_dtype=kv_dtype,
                               lookahead=lookahead, prefill_chunk=prefill_chunk,
                               kv_layout=kv_layout, page_size=page_size,
-                              kv_pages=kv_pages)
+                              kv_pages=kv_pages, weight_dtype=weight_dtype)
         for p_ids, new in zip(prompts, outs):
             if tok is not None:
                 from ..utils.tokenizer import decode as tok_decode
@@ -963,6 +981,9 @@ def serve_cmd(
     kv_pages: Optional[int] = typer.Option(None, "--kv-pages", help=(
         "pages in the paged KV pool per layer (default: the contiguous "
         "cache's capacity)")),
+    weight_dtype: str = typer.Option("bf16", "--weight-dtype",
+                                     callback=_weight_dtype_option,
+                                     help=_WEIGHT_DTYPE_HELP),
 ):
     """Serve the model over an OpenAI-style HTTP API (engine-side
     counterpart of the reference's hosted inference surface):
@@ -985,7 +1006,7 @@ def serve_cmd(
     uvicorn.run(create_app(m, model, tok, max_batch=max_batch,
                            batch_window_ms=batch_window_ms, kv_dtype=kv_dtype,
                            kv_layout=kv_layout, page_size=page_size,
-                           kv_pages=kv_pages),
+                           kv_pages=kv_pages, weight_dtype=weight_dtype),
                 host=host, port=port,
                 log_level="warning")
 

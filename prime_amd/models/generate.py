@@ -19,6 +19,7 @@ from .llama import Llama
 
 KV_DTYPES = ("bf16", "fp8")
 KV_LAYOUTS = ("contiguous", "paged")
+WEIGHT_DTYPES = ("bf16", "fp8")
 
 
 def _pad64(n: int) -> int:
@@ -186,6 +187,7 @@ def generate_batch(
     kv_layout: str = "contiguous",
     page_size: int = 64,
     kv_pages: int | None = None,
+    weight_dtype: str = "bf16",
 ) -> list[list[int]]:
     """Ragged batched generation: `prompts` is a list of token-id lists of
     different lengths; returns the NEW tokens of each. max_new_tokens,
@@ -242,7 +244,15 @@ def generate_batch(
     the longest length. The prompts always enter through the chunked ragged
     prefill (prefill_chunk, or 256 tokens a step); the decode graph reads the
     table from a stable device buffer, and its session key carries the
-    layout, the page size and the pool size."""
+    layout, the page size and the pool size.
+
+    weight_dtype "fp8" (a model on the GPU) reads every projection whose shape
+    qualifies (Llama.quantize_decode_weights) as e4m3 bytes with one scale per
+    output channel in the calls of at most 64 rows, the decode steps above
+    all: half the weight traffic through ops.linear_w8. The fp8 copies are
+    made once per model and kept on it until a weight changes; the bf16
+    weights stay and serve the prefill and every larger call. The dtype is
+    part of every session key; "bf16" leaves everything as it was."""
     lookahead = int(lookahead)
     prefill_chunk = int(prefill_chunk)
     if prefill_chunk < 0 or prefill_chunk % 8 != 0:
@@ -256,6 +266,9 @@ def generate_batch(
     if kv_layout not in KV_LAYOUTS:
         raise ValueError(f"kv_layout must be one of {KV_LAYOUTS} (got "
                          f"{kv_layout!r})")
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES} (got "
+                         f"{weight_dtype!r})")
     paged = kv_layout == "paged"
     if paged:
         if kv_dtype != "bf16" or lookahead:
@@ -275,6 +288,9 @@ def generate_batch(
         raise ValueError("prefill_chunk with kv_dtype='fp8' needs a model on "
                          "the GPU: chunked prefill over an fp8 cache has no "
                          "host path")
+    if weight_dtype == "fp8" and dev.type != "cuda":
+        raise ValueError("weight_dtype='fp8' needs a model on the GPU: the "
+                         "fp8 weight copies are read by a HIP kernel only")
     if lookahead and kv_dtype != "bf16" and dev.type != "cuda":
         # the model's guard (Attention.forward), raised before any work
         raise NotImplementedError("lookahead decoding over an fp8 KV cache "
@@ -318,65 +334,100 @@ def generate_batch(
     sessions = getattr(model, "_decode_sessions", None)
     if sessions is None:
         sessions = model._decode_sessions = {}
-    key = ("ragged", Bk, smax, dev.index, kv_dtype) if not lookahead \
-        else ("ragged_multi", Bk, smax, dev.index, lookahead + 1, kv_dtype)
+    key = ("ragged", Bk, smax, dev.index, weight_dtype, kv_dtype) \
+        if not lookahead else ("ragged_multi", Bk, smax, dev.index,
+                               lookahead + 1, weight_dtype, kv_dtype)
     if paged:
-        key = ("ragged_paged", Bk, smax, dev.index, P, n_pool)
-    sess = sessions.get(key) if graphing else None
-    if sess is None:
+        key = ("ragged_paged", Bk, smax, dev.index, weight_dtype, P, n_pool)
+    # with "fp8" the projections carry their fp8 copies for this call only, so
+    # that a later "bf16" call finds the model as it was
+    before = _attach_decode_weights(model, sessions) \
+        if weight_dtype == "fp8" else []
+    try:
+        sess = sessions.get(key) if graphing else None
+        if sess is None:
+            if paged:
+                # one table for all layers; its pointer is what the graph reads
+                table = torch.full((Bk, smax // P), -1, dtype=torch.int32,
+                                   device=dev)
+                caches = [ops.KVCachePaged(
+                    torch.zeros(n_pool, P, cfg.n_kv_heads, cfg.head_dim,
+                                device=dev, dtype=dtype),
+                    torch.zeros(n_pool, P, cfg.n_kv_heads, cfg.head_dim,
+                                device=dev, dtype=dtype), table)
+                    for _ in range(cfg.n_layers)]
+            elif kv_dtype == "fp8":
+                caches = [ops.kv_cache_fp8(Bk, smax, cfg.n_kv_heads, cfg.head_dim, dev)
+                          for _ in range(cfg.n_layers)]
+            else:
+                caches = [
+                    (
+                        torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
+                        torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
+                    )
+                    for _ in range(cfg.n_layers)
+                ]
+            sess = _ragged_state(caches, Bk, dev)
+            sess["weight_dtype"] = weight_dtype
+            if paged:
+                sess["pages"] = ops.KVPageAllocator(n_pool)
+            if lookahead:
+                sess["tok"] = torch.zeros(Bk, lookahead + 1, dtype=torch.int64,
+                                          device=dev)
+                sess["n_new"] = torch.ones(Bk, dtype=torch.int32, device=dev)
+            if graphing:
+                # capture BEFORE prefill, as _build_session does: the warmup and
+                # capture passes write junk rows that the prefill overwrites
+                _capture_ragged(model, sess, _multi_step if lookahead
+                                else _ragged_step)
+                sessions[key] = sess
+        caches = sess["caches"]
         if paged:
-            # one table for all layers; its pointer is what the graph reads
-            table = torch.full((Bk, smax // P), -1, dtype=torch.int32,
-                               device=dev)
-            caches = [ops.KVCachePaged(
-                torch.zeros(n_pool, P, cfg.n_kv_heads, cfg.head_dim,
-                            device=dev, dtype=dtype),
-                torch.zeros(n_pool, P, cfg.n_kv_heads, cfg.head_dim,
-                            device=dev, dtype=dtype), table)
-                for _ in range(cfg.n_layers)]
-        elif kv_dtype == "fp8":
-            caches = [ops.kv_cache_fp8(Bk, smax, cfg.n_kv_heads, cfg.head_dim, dev)
-                      for _ in range(cfg.n_layers)]
-        else:
-            caches = [
-                (
-                    torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
-                    torch.zeros(Bk, smax, cfg.n_kv_heads, cfg.head_dim, device=dev, dtype=dtype),
-                )
-                for _ in range(cfg.n_layers)
-            ]
-        sess = _ragged_state(caches, Bk, dev)
-        if paged:
-            sess["pages"] = ops.KVPageAllocator(n_pool)
-        if lookahead:
-            sess["tok"] = torch.zeros(Bk, lookahead + 1, dtype=torch.int64,
-                                      device=dev)
-            sess["n_new"] = torch.ones(Bk, dtype=torch.int32, device=dev)
-        if graphing:
-            # capture BEFORE prefill, as _build_session does: the warmup and
-            # capture passes write junk rows that the prefill overwrites
-            _capture_ragged(model, sess, _multi_step if lookahead
-                            else _ragged_step)
-            sessions[key] = sess
-    caches = sess["caches"]
-    if paged:
-        # the call's pages; handed back (and the table cleared) when it ends
-        held = [sess["pages"].alloc(need[b]) for b in range(n)]
-        rows = torch.full(tuple(caches[0].table.shape), -1, dtype=torch.int32)
-        for b in range(n):
-            rows[b, :need[b]] = torch.tensor(held[b], dtype=torch.int32)
-        caches[0].table.copy_(rows)
-        try:
-            return _generate_ragged(model, sess, prompts, max_new, temps,
-                                    topks, seeds, stops, out, done, graphing,
-                                    0, prefill_chunk or 256)
-        finally:
-            for ids in held:
-                sess["pages"].free(ids)
-            caches[0].table.fill_(-1)
-    return _generate_ragged(model, sess, prompts, max_new, temps, topks, seeds,
-                            stops, out, done, graphing, lookahead,
-                            prefill_chunk)
+            # the call's pages; handed back (and the table cleared) when it ends
+            held = [sess["pages"].alloc(need[b]) for b in range(n)]
+            rows = torch.full(tuple(caches[0].table.shape), -1, dtype=torch.int32)
+            for b in range(n):
+                rows[b, :need[b]] = torch.tensor(held[b], dtype=torch.int32)
+            caches[0].table.copy_(rows)
+            try:
+                return _generate_ragged(model, sess, prompts, max_new, temps,
+                                        topks, seeds, stops, out, done, graphing,
+                                        0, prefill_chunk or 256)
+            finally:
+                for ids in held:
+                    sess["pages"].free(ids)
+                caches[0].table.fill_(-1)
+        return _generate_ragged(model, sess, prompts, max_new, temps, topks, seeds,
+                                stops, out, done, graphing, lookahead,
+                                prefill_chunk)
+    finally:
+        for m, lw in before:
+            if lw is None:
+                m.__dict__.pop("w8", None)
+            else:
+                m.w8 = lw
+
+
+def _attach_decode_weights(model, sessions) -> list:
+    """Set the fp8 weight copies on the model's projections, quantising only
+    when a weight has changed since the cached copies were made (keyed on the
+    weights' storage and _version). Returns what the modules carried before,
+    [(module, w8 or None)]."""
+    mods = model._prime_linears()
+    before = [(m, m.__dict__.get("w8")) for m in mods]
+    wkey = tuple((m.weight.data_ptr(), m.weight._version) for m in mods)
+    cached = getattr(model, "_decode_w8", None)
+    if cached is not None and cached[0] == wkey:
+        for m, lw in cached[1]:
+            m.w8 = lw
+        return before
+    model.drop_decode_weights()
+    model.quantize_decode_weights()
+    model._decode_w8 = (wkey, [(m, m.w8) for m in mods if m.w8 is not None])
+    # graphs captured over the previous copies would read freed memory
+    for k in [k for k, v in sessions.items() if v.get("weight_dtype") == "fp8"]:
+        del sessions[k]
+    return before
 
 
 def _generate_ragged(model, sess, prompts, max_new, temps, topks, seeds, stops,

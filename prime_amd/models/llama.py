@@ -27,9 +27,24 @@ class PrimeLinear(nn.Linear):
     (ops.tuned_linear): NT forward, NT dX against a per-step cached W^T,
     NN dW via an LDS-tiled dY transpose (the qkv and gate/up projections go
     through ops.qkv_rope / ops.gateup_swiglu instead, whose backward
-    kernels emit dY^T themselves). State-dict compatible with nn.Linear."""
+    kernels emit dY^T themselves). State-dict compatible with nn.Linear.
+
+    `w8` is an optional fp8 copy of the weight (ops.LinearW8; a plain
+    attribute, not a parameter and not in the state dict), set by
+    Llama.quantize_decode_weights(). A call on the GPU with at most 64 rows
+    and grad disabled, i.e. a decode step, reads it through ops.linear_w8
+    instead of the bf16 weight; every other call is untouched."""
+
+    w8 = None
+
+    def use_w8(self, x) -> bool:
+        return (self.w8 is not None and x.is_cuda
+                and not torch.is_grad_enabled()
+                and x.numel() // x.shape[-1] <= ops.LINEAR_W8_MAX_ROWS)
 
     def forward(self, x):
+        if self.use_w8(x):
+            return ops.linear_w8(x, self.w8)
         return ops.tuned_linear(x, self.weight)
 
 
@@ -226,6 +241,8 @@ class MLP(nn.Module):
     def forward(self, x):
         # projection + swiglu as one op: its backward emits dgu and dgu^T in
         # one pass (composes the plain ops when the shape does not tile)
+        if self.w_gateup.use_w8(x):  # decode step over the fp8 weight copy
+            return self.w_down(ops.swiglu(ops.linear_w8(x, self.w_gateup.w8)))
         return self.w_down(ops.gateup_swiglu(x, self.w_gateup.weight))
 
 
@@ -290,6 +307,28 @@ class Llama(nn.Module):
         )
         self.rope_cos = cos
         self.rope_sin = sin
+
+    def _prime_linears(self):
+        return [m for m in self.modules() if isinstance(m, PrimeLinear)]
+
+    def quantize_decode_weights(self) -> int:
+        """Give every PrimeLinear whose shape ops.quant_weight_fp8 takes
+        (N % 64 == 0, K % 256 == 0) an fp8 copy of its weight, `w8`, which
+        decode-sized calls then read (PrimeLinear). Returns how many were
+        set; calling it again re-quantises. The bf16 weights stay: prefill
+        and calls with more than 64 rows use them."""
+        n = 0
+        for m in self._prime_linears():
+            N, K = m.weight.shape
+            if N % 64 == 0 and K % 256 == 0:
+                m.w8 = ops.quant_weight_fp8(m.weight)
+                n += 1
+        return n
+
+    def drop_decode_weights(self) -> None:
+        """Remove the fp8 weight copies of quantize_decode_weights()."""
+        for m in self._prime_linears():
+            m.__dict__.pop("w8", None)
 
     def forward(self, tokens: torch.Tensor, caches=None, pos: int = 0,
                 pos_dev=None, doc_start=None, seq_pos=None) -> torch.Tensor:

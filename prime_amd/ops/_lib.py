@@ -72,6 +72,7 @@ _SIGS = {
     "prime_attn_prefill_ragged_paged": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 9 + [ctypes.c_double],
     "prime_decode_qkv_append_paged": [ctypes.c_void_p] * 9 + [ctypes.c_int64] * 8,
     "prime_prefill_qkv_append_paged": [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 9,
+    "prime_linear_w8": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 4,
     "prime_gemm_nt": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 4,
     "prime_gemm_nt8": [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 4,
     "prime_quant_fp8": [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 2,

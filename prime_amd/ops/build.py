@@ -21,7 +21,7 @@ ARCH = os.environ.get("PRIME_AMD_ARCH", "gfx950")
 NO_PACKED_FP32 = ("decode_multi.hip", "decode_multi_fp8.hip",
                   "prefill_ragged.hip", "prefill_ragged_fp8.hip",
                   "decode_ragged_paged.hip", "prefill_ragged_paged.hip",
-                  "append_paged.hip")
+                  "append_paged.hip", "linear_w8.hip")
 _NO_PACKED_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

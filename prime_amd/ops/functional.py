@@ -2283,3 +2283,122 @@ def mfma_probe32(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     C = torch.empty(32, 32, device=A.device, dtype=torch.float32)
     check(lib().prime_mfma_probe32(stream_of(A), ptr(A), ptr(B), ptr(C)), "mfma_probe32")
     return C
+
+
+# ------------------------------------------------- weight-only fp8 linear
+class LinearW8(NamedTuple):
+    """An fp8 (e4m3) copy of a linear weight [N, K] for decode-sized batches.
+    Row-wise convention with one output channel as the row: m = max(max|w[n,
+    :]|, 1e-12), s = 448 / m, sinv[n] = m / 448 (fp32), byte = e4m3_rne(
+    clamp(w * s, -448, 448)); the value held is float(byte) * sinv[n].
+    w8: uint8 [N/16, K/64, 64, 16], pre-shuffled so that every wave load of
+    the kernel is one linear 1 KiB: the 16 bytes of lane l = lg*16 + li in
+    tile (nt, kc) are row nt*16 + li, columns kc*64 + lg*16 .. +15.
+    sinv: fp32 [N]."""
+    w8: torch.Tensor
+    sinv: torch.Tensor
+    N: int
+    K: int
+
+
+LINEAR_W8_MAX_ROWS = 64
+_LINEAR_W8_CHUNK = 256  # columns per K step of the kernel
+_LINEAR_W8_WS: dict = {}  # (M, N, ksplit, device) -> fp32 partials
+
+
+def quant_weight_fp8(w: torch.Tensor) -> LinearW8:
+    """Quantise a weight [N, K] (N % 64 == 0, K % 256 == 0) to LinearW8."""
+    if w.dim() != 2:
+        raise ValueError(f"quant_weight_fp8 needs a [N, K] weight (got "
+                         f"{tuple(w.shape)})")
+    N, K = w.shape
+    if N == 0 or K == 0 or N % 64 != 0 or K % _LINEAR_W8_CHUNK != 0:
+        raise ValueError(f"quant_weight_fp8 needs N % 64 == 0 and K % "
+                         f"{_LINEAR_W8_CHUNK} == 0 (got N={N}, K={K})")
+    w = w.detach()
+    if _is_hip(w):
+        q, sinv = _quant_rowwise_fp8(w.to(torch.bfloat16).contiguous())
+        sinv = sinv.view(N)
+    else:
+        q, sinv = _kv_quant(w)
+    w8 = q.view(torch.uint8).view(N // 16, 16, K // 64, 4, 16) \
+        .permute(0, 2, 3, 1, 4).reshape(N // 16, K // 64, 64, 16).contiguous()
+    return LinearW8(w8, sinv.contiguous(), N, K)
+
+
+def _check_w8(lw, what: str) -> None:
+    if not isinstance(lw, LinearW8):
+        raise TypeError(f"{what} needs a LinearW8 (got {type(lw).__name__})")
+    if lw.w8.dtype != torch.uint8 or lw.sinv.dtype != torch.float32 \
+            or lw.w8.shape != (lw.N // 16, lw.K // 64, 64, 16) \
+            or lw.sinv.shape != (lw.N,) or lw.N % 64 or lw.K % _LINEAR_W8_CHUNK:
+        raise ValueError(f"{what}: inconsistent LinearW8")
+
+
+def weight_fp8_dequant(lw: LinearW8) -> torch.Tensor:
+    """The weight a LinearW8 holds, as fp32 [N, K]: the executable definition
+    of the format."""
+    _check_w8(lw, "weight_fp8_dequant")
+    b = lw.w8.view(lw.N // 16, lw.K // 64, 4, 16, 16).permute(0, 3, 1, 2, 4) \
+        .reshape(lw.N, lw.K)
+    return b.view(torch.float8_e4m3fn).float() * lw.sinv.unsqueeze(-1)
+
+
+def linear_w8_split(N: int, K: int, n_cu: int = 256) -> int:
+    """K ranges (grid.y) of linear_w8 for a weight shape: a divisor of K/256
+    aiming at about two workgroups (64 output rows each) per CU while every
+    range keeps at least two 256-column chunks. Depends on the launch shape
+    only, so it is stable under graph replay."""
+    chunks = K // _LINEAR_W8_CHUNK
+    want = min(-(-2 * n_cu // (N // 64)), max(1, chunks // 2))
+    return max(d for d in range(1, chunks + 1) if chunks % d == 0 and d <= want)
+
+
+def linear_w8(x: torch.Tensor, lw: LinearW8, ksplit=None) -> torch.Tensor:
+    """x [..., K] (1 <= rows <= 64) times an fp8 weight: y[m, n] = sinv[n] *
+    sum_k x[m, k] * dec(byte[n, k]), summed in fp32, scaled once and rounded
+    to x's dtype. No float atomics: two calls are bit-identical. `ksplit`
+    overrides linear_w8_split (a divisor of K/256)."""
+    _check_w8(lw, "linear_w8")
+    N, K = lw.N, lw.K
+    if x.shape[-1] != K:
+        raise ValueError(f"linear_w8: x {tuple(x.shape)} does not match "
+                         f"K={K}")
+    M = x.numel() // K
+    if M > LINEAR_W8_MAX_ROWS:
+        raise NotImplementedError(
+            f"linear_w8 takes at most {LINEAR_W8_MAX_ROWS} rows (got {M}); "
+            "larger batches use the bf16 weight")
+    if M < 1:
+        raise ValueError("linear_w8 needs at least one row")
+    if lw.w8.device != x.device:
+        raise ValueError("linear_w8: x and the weight are on different devices")
+    if not _is_hip(x):
+        y = torch.nn.functional.linear(x.float(), weight_fp8_dequant(lw))
+        return y.to(x.dtype)
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"linear_w8 needs bf16 x (got {x.dtype})")
+    chunks = K // _LINEAR_W8_CHUNK
+    if ksplit is None:
+        ksplit = linear_w8_split(N, K, _n_cu(x.device))
+    if ksplit < 1 or chunks % ksplit != 0:
+        raise ValueError(f"ksplit must divide K/{_LINEAR_W8_CHUNK} = {chunks} "
+                         f"(got {ksplit})")
+    ws = None
+    if ksplit > 1:
+        # one workspace per shape, reused: a captured graph sees stable pointers
+        key = (M, N, ksplit, x.device.index)
+        ws = _LINEAR_W8_WS.get(key)
+        if ws is None:
+            ws = _LINEAR_W8_WS[key] = torch.empty(
+                ksplit, M, N, device=x.device, dtype=torch.float32)
+    x2 = x.reshape(M, K).contiguous()
+    y = torch.empty(*x.shape[:-1], N, device=x.device, dtype=x.dtype)
+    check(
+        lib().prime_linear_w8(
+            stream_of(x2), ptr(x2), ptr(lw.w8), ptr(lw.sinv), ptr(y), ptr(ws),
+            M, N, K, ksplit,
+        ),
+        "linear_w8",
+    )
+    return y

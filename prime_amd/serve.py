@@ -55,7 +55,8 @@ class ChatRequest(BaseModel):
 def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                batch_window_ms: float = 5.0, kv_dtype: str = "bf16",
                prefill_chunk: int = 0, kv_layout: str = "contiguous",
-               page_size: int = 64, kv_pages: Optional[int] = None):
+               page_size: int = 64, kv_pages: Optional[int] = None,
+               weight_dtype: str = "bf16"):
     from fastapi import FastAPI, HTTPException
 
     from .models import generate as gen_mod
@@ -70,6 +71,9 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                          f"{kv_layout!r})")
     if kv_layout == "paged" and kv_dtype != "bf16":
         raise ValueError("kv_layout='paged' stores a bf16 cache")
+    if weight_dtype not in gen_mod.WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of "
+                         f"{gen_mod.WEIGHT_DTYPES} (got {weight_dtype!r})")
     # with kv_dtype "fp8" generate_batch decides (a model on the GPU)
     if prefill_chunk < 0 or prefill_chunk % 8 != 0:
         raise ValueError("prefill_chunk must be 0 or a positive multiple of 8")
@@ -97,7 +101,8 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
                     seed=[r.seed for _, r, _ in items],
                     stop_token_ids=list(stop), kv_dtype=kv_dtype,
                     prefill_chunk=prefill_chunk, kv_layout=kv_layout,
-                    page_size=page_size, kv_pages=kv_pages)
+                    page_size=page_size, kv_pages=kv_pages,
+                    weight_dtype=weight_dtype)
                 for (_, _, fut), new in zip(items, outs):
                     fut.set_result(new)
             except Exception as e:  # noqa: BLE001 - reported to every caller
@@ -180,7 +185,8 @@ def create_app(model, model_name: str, tokenizer=None, max_batch: int = 8,
     @app.get("/health")
     def health():
         return {"status": "ok", "model": model_name, "device": str(dev),
-                "kv_dtype": kv_dtype, "kv_layout": kv_layout}
+                "kv_dtype": kv_dtype, "kv_layout": kv_layout,
+                "weight_dtype": weight_dtype}
 
     @app.get("/v1/models")
     def models():
