@@ -15,14 +15,14 @@
 //    is a shuffle reduction inside the sub-group.
 //  - prime_kv_store_fp8: prefill store of k, v [B,S,Hkv,D] into rows
 //    [pos, pos+S) of a cache [B',Smax,Hkv,D] (D/4 lanes x 8 B per row).
-//  - prime_attn_decode_ragged_fp8: attn_decode_ragged_kernel's grid, lens
-//    clamp, idle / empty-split rule, workspace layout and index-order merge
-//    (decode_ragged.hip), streaming 1-byte elements: K rows in 16 B loads
-//    with the score scaled by k_scale[row], P * v_scale[row] into LDS, V rows
-//    coalesced at 8 B per lane with no scale handling.
+//  - prime_attn_decode_ragged_fp8: the grid, lens clamp, idle / empty-split
+//    rule and workspace layout of the bf16 kernel and its index-order merge
+//    itself (decode_ragged_common.h), streaming 1-byte elements: K rows in
+//    16 B loads with the score scaled by k_scale[row], P * v_scale[row] into
+//    LDS, V rows coalesced at 8 B per lane with no scale handling.
 // The e4m3 decode is the gfx950 conversion instruction, which is OCP (not
 // fnuz) on this target.
-#include "common.h"
+#include "decode_ragged_common.h"
 #include <hip/hip_fp8.h>
 
 #define DF_CHUNK 256    // keys per online-softmax chunk (= DR_CHUNK)
@@ -413,63 +413,6 @@ __global__ __launch_bounds__(DF_THREADS) void attn_decode_ragged_fp8_kernel(
   }
 }
 
-// This file's copy of attn_decode_merge_kernel (decode_ragged.hip): the
-// library is one non-RDC compile, so a kernel of another file cannot be
-// launched from here. Splits are combined in index order.
-__global__ void attn_decode_merge_fp8_kernel(const float* __restrict__ ws,
-                                             bf16* __restrict__ O, int H,
-                                             int Hkv, int D, int nsplit) {
-  const int bh = blockIdx.x;
-  const int b = bh / H, h = bh - b * H;
-  const int G = H / Hkv;
-  const int hkv = h / G, g = h - hkv * G;
-  const int d = threadIdx.x;
-  const int part = G * (D + 2);
-  const float* base = ws + ((int64_t)b * Hkv + hkv) * nsplit * part;
-  float M = -1e30f;
-  for (int s = 0; s < nsplit; ++s)
-    M = fmaxf(M, base[(int64_t)s * part + G * D + g]);
-  float num = 0.f, den = 0.f;
-  for (int s = 0; s < nsplit; ++s) {
-    const float* ps = base + (int64_t)s * part;
-    const float w = __expf(ps[G * D + g] - M);
-    den += w * ps[G * D + G + g];
-    num += w * ps[g * D + d];
-  }
-  // every split empty (idle slot): num = den = 0 -> exactly zero
-  O[((int64_t)b * H + h) * D + d] = f2bf(num / fmaxf(den, 1e-30f));
-}
-
-template <int D, int G>
-static void launch_ragged_fp8(hipStream_t stream, const void* Q, const void* K,
-                              const void* V, const void* Ks, const void* Vs,
-                              void* ws, const void* lens, int B, int H,
-                              int Hkv, int Smax, int split_rows, int nsplit,
-                              float scale) {
-  hipLaunchKernelGGL((attn_decode_ragged_fp8_kernel<D, G>),
-                     dim3(B * Hkv, nsplit), dim3(DF_THREADS), 0, stream,
-                     (const bf16*)Q, (const unsigned char*)K,
-                     (const unsigned char*)V, (const float*)Ks,
-                     (const float*)Vs, (float*)ws, (const int*)lens, H, Hkv,
-                     Smax, split_rows, scale);
-}
-
-template <int D>
-static int launch_ragged_fp8_g(int G, hipStream_t stream, const void* Q,
-                               const void* K, const void* V, const void* Ks,
-                               const void* Vs, void* ws, const void* lens,
-                               int B, int H, int Hkv, int Smax, int split_rows,
-                               int nsplit, float scale) {
-  switch (G) {
-    case 1: launch_ragged_fp8<D, 1>(stream, Q, K, V, Ks, Vs, ws, lens, B, H, Hkv, Smax, split_rows, nsplit, scale); break;
-    case 2: launch_ragged_fp8<D, 2>(stream, Q, K, V, Ks, Vs, ws, lens, B, H, Hkv, Smax, split_rows, nsplit, scale); break;
-    case 4: launch_ragged_fp8<D, 4>(stream, Q, K, V, Ks, Vs, ws, lens, B, H, Hkv, Smax, split_rows, nsplit, scale); break;
-    case 8: launch_ragged_fp8<D, 8>(stream, Q, K, V, Ks, Vs, ws, lens, B, H, Hkv, Smax, split_rows, nsplit, scale); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipSuccess;
-}
-
 // Same contract as prime_attn_decode_ragged (ws layout, split_rows a
 // positive multiple of the chunk chosen from the launch shape only), with
 // the cache as e4m3 bytes K/V [B,Smax,Hkv,D] + fp32 k_scale/v_scale
@@ -479,29 +422,18 @@ PRIME_API int prime_attn_decode_ragged_fp8(
     const void* k_scale, const void* v_scale, void* O, void* ws,
     const void* lens, int64_t B, int64_t H, int64_t Hkv, int64_t Smax,
     int64_t D, int64_t split_rows, double scale) {
-  if ((D != 64 && D != 128) || B < 1 || H < 1 || Hkv < 1 || Smax < 1 ||
-      H % Hkv != 0 || split_rows < DF_CHUNK || split_rows % DF_CHUNK != 0 ||
-      !ws || !lens || !k_scale || !v_scale)
+  if (dr_check_args(B, H, Hkv, Smax, D, split_rows, ws, lens) || !k_scale ||
+      !v_scale)
     return hipErrorInvalidValue;
-  const int64_t G = H / Hkv;
-  if (G != 1 && G != 2 && G != 4 && G != 8) return hipErrorInvalidValue;
   const int64_t nsplit = (Smax + split_rows - 1) / split_rows;
-  if (nsplit > 65535 || B * Hkv > 0x7fffffff || B * H > 0x7fffffff ||
-      Smax > 0x7fffffff - split_rows)
-    return hipErrorInvalidValue;
-  int rc;
-  if (D == 128)
-    rc = launch_ragged_fp8_g<128>((int)G, stream, Q, K, V, k_scale, v_scale,
-                                  ws, lens, (int)B, (int)H, (int)Hkv,
-                                  (int)Smax, (int)split_rows, (int)nsplit,
-                                  (float)scale);
-  else
-    rc = launch_ragged_fp8_g<64>((int)G, stream, Q, K, V, k_scale, v_scale, ws,
-                                 lens, (int)B, (int)H, (int)Hkv, (int)Smax,
-                                 (int)split_rows, (int)nsplit, (float)scale);
-  if (rc != hipSuccess) return rc;
-  hipLaunchKernelGGL(attn_decode_merge_fp8_kernel, dim3((int)(B * H)),
-                     dim3((int)D), 0, stream, (const float*)ws, (bf16*)O,
-                     (int)H, (int)Hkv, (int)D, (int)nsplit);
-  return (int)hipGetLastError();
+  dr_dispatch(D, H / Hkv, [&](auto d, auto g) {
+    hipLaunchKernelGGL((attn_decode_ragged_fp8_kernel<d(), g()>),
+                       dim3((int)(B * Hkv), (int)nsplit), dim3(DF_THREADS), 0,
+                       stream, (const bf16*)Q, (const unsigned char*)K,
+                       (const unsigned char*)V, (const float*)k_scale,
+                       (const float*)v_scale, (float*)ws, (const int*)lens,
+                       (int)H, (int)Hkv, (int)Smax, (int)split_rows,
+                       (float)scale);
+  });
+  return dr_launch_merge(stream, ws, O, B, H, Hkv, D, nsplit);
 }

@@ -1,15 +1,20 @@
 // What the chunked ragged prefill kernels share (prefill_ragged.hip over the
-// bf16 cache, prefill_ragged_fp8.hip over the fp8 cache): the tile constants,
-// the (lens, n_new) clamp, the swizzles of the two LDS images with the
-// fragment reads that undo them, the MFMA / pack helpers, the empty-split
-// and epilogue stores and the merge kernel. The library is one non-RDC
-// compile per file, so the kernels here are `static`: each file gets its own
-// copy, and the swizzle a file stages with cannot drift from the XOR the
-// fragment reads apply.
+// bf16 cache, prefill_ragged_paged.hip over the paged bf16 cache,
+// prefill_ragged_fp8.hip over the fp8 cache): the tile constants, the
+// (lens, n_new) clamp, the swizzles of the two LDS images with the fragment
+// reads that undo them, the MFMA / pack helpers, the empty-split and
+// epilogue stores, the merge kernel, the argument checks and the dispatch;
+// and, for the two bf16 files, the LDS-DMA stage and the whole kernel body
+// (pf_body) over a tile-source policy. The library is one non-RDC compile
+// per file, so the kernels here are `static`: each file gets its own copy,
+// and the swizzle a file stages with cannot drift from the XOR the fragment
+// reads apply.
 //
-// Both including files are compiled without the packed fp32 VALU
+// All including files are compiled without the packed fp32 VALU
 // instructions (ops/build.py, NO_PACKED_FP32).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
@@ -186,6 +191,218 @@ __device__ __forceinline__ void pf_epilogue(const f32x16 (&o_acc)[D / 32],
   }
 }
 
+// Stage keys [kb, kb + 64) of one (b, kv head) into `tile`; rows past `last`
+// re-read row `last`. `gbase` is the (block-uniform) address logical row 0 of
+// the tile's source has: the slab of a contiguous cache, or, for a page, its
+// base minus its first logical row; every row read is in [kb, max(kb, last)].
+// 256 lanes, 16 B each, D/32 rounds. The swizzle of the image is applied
+// through the SOURCE address: LDS-DMA writes linearly.
+template <int D, bool VTILE>
+__device__ __forceinline__ void pf_stage(const bf16* __restrict__ gbase,
+                                         int64_t row_stride, int kb, int last,
+                                         bf16* tile, int tid) {
+  constexpr int UPR = D / 8;  // 16 B units per row
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i) {
+    const int u = i * PF_THREADS + tid;
+    const int row = u / UPR;
+    const int colb =
+        ((u % UPR) * 16) ^ (VTILE ? pf_vswz<D>(row) : pf_kswz<D>(row));
+    const bf16* src =
+        gbase + (int64_t)min(kb + row, last) * row_stride + colb / 2;
+    // linear destination: wave-uniform base + lane * 16
+    lds_char* dst = (lds_char*)tile + i * (PF_THREADS * 16) + (tid >> 6) * 1024;
+    __builtin_amdgcn_global_load_lds((g_void*)src, (lds_void*)dst, 16, 0, 0);
+  }
+}
+
+// s_waitcnt vmcnt(0): this wave's loads, LDS-DMA included, have landed
+__device__ __forceinline__ void pf_wait_loads() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
+// The bf16 prefill kernel (the structure is described in prefill_ragged.hip).
+// Where a key tile comes from is asked of a `Src` policy, a small struct
+// built by the __global__ wrapper from its kernel arguments:
+//   src.open(b, col, stride, r0, r1)  once, behind the empty-split return
+//   src.off(kb, first)                element offset, from src.Kb / src.Vb, of
+//                                     the pf_stage base of tile kb; `first`:
+//                                     the split's first tile
+//   src.prefetch(kb, r1)              behind the stage of the tile before kb
+// so the contiguous and the paged kernel are one text.
+template <int D, int GSH, class Src>
+__device__ __forceinline__ void pf_body(
+    const bf16* __restrict__ Q, bf16* __restrict__ O, float* __restrict__ ws,
+    const int* __restrict__ lens, const int* __restrict__ n_new, int T, int H,
+    int Hkv, int Smax, int split_rows, float scale, Src src) {
+  constexpr int G = 1 << GSH;
+  constexpr int QT = PF_Q_ROWS / G;  // tokens per q-tile
+  constexpr int DSL = D / 16;        // k-steps of the score MFMA
+  constexpr int DT32 = D / 32;       // 32-wide d tiles of O^T
+  const int qt = gridDim.x - 1 - blockIdx.x;  // longest trips first
+  const int bk = blockIdx.y;
+  const int b = bk / Hkv, hkv = bk - b * Hkv;
+  const int sp = blockIdx.z, nsplit = gridDim.z;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wid = tid >> 6;
+  const int lo = lane & 31, hi = lane >> 5;
+  const int M = T * G;
+  int L0, n;
+  pf_live(lens, n_new, b, T, Smax, L0, n);
+
+  const int t0 = qt * QT;                 // first token of the tile
+  const int tl = min(t0 + QT, n) - 1;     // its last LIVE token
+  const int row0 = qt * PF_Q_ROWS;
+  const int r0 = sp * split_rows;
+  const int r1 = tl >= t0 ? min(r0 + split_rows, L0 + tl) : 0;
+  // partials of this (b, kv head, split)
+  const int64_t prow = ((int64_t)bk * nsplit + sp) * M;
+  float* ws_o = ws + prow * D;
+  float* ws_ml = ws + (int64_t)gridDim.y * nsplit * M * D + prow * 2;
+
+  if (r0 >= r1) {  // block-uniform: nothing live here; no cache row touched
+    pf_write_empty<D, GSH>(O, ws_o, ws_ml, row0, M, nsplit, b, hkv, T, H, tid);
+    return;
+  }
+
+  __shared__ __attribute__((aligned(1024))) bf16 k_lds[2][PF_KEY_TILE * D];
+  __shared__ __attribute__((aligned(1024))) bf16 v_lds[2][PF_KEY_TILE * D];
+
+  const int64_t row_stride = (int64_t)Hkv * D;
+  src.open(b, (int64_t)hkv * D, row_stride, r0, r1);
+  const int last = r1 - 1;  // tile loads past the range re-read this row
+
+  // ---- this lane's query row; rows of dead tokens run on zeros
+  const int myrow = row0 + wid * 32 + lo;
+  const int my_t = myrow >> GSH, my_g = myrow & (G - 1);
+  const bool live = my_t < n;
+  const int64_t qo_off =
+      (((int64_t)b * T + my_t) * H + hkv * G + my_g) * D;  // used if my_t < T
+  short8 qf[DSL];
+#pragma unroll
+  for (int ds = 0; ds < DSL; ++ds) {
+    qf[ds] = short8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (live)
+      qf[ds] = *reinterpret_cast<const short8*>(Q + qo_off + ds * 16 + hi * 8);
+  }
+  const int lim = min(r1, L0 + my_t);  // first key this row may NOT see
+  // wave-uniform: first / last live token of the wave
+  const int tw0 = (row0 + wid * 32) >> GSH;
+  const int twl = min((row0 + wid * 32 + 31) >> GSH, tl);
+  const int kend_w = tw0 < n ? min(r1, L0 + twl) : 0;
+  const int lim_min = min(r1, L0 + tw0);
+
+  float m_run = PF_NEG, l_run = 0.f;
+  f32x16 o_acc[DT32];
+#pragma unroll
+  for (int dt = 0; dt < DT32; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o_acc[dt][r] = 0.f;
+
+  {
+    const int64_t off = src.off(r0, true);
+    pf_stage<D, false>(src.Kb + off, row_stride, r0, last, k_lds[0], tid);
+    pf_stage<D, true>(src.Vb + off, row_stride, r0, last, v_lds[0], tid);
+  }
+  for (int kb = r0, it = 0; kb < r1; kb += PF_KEY_TILE, ++it) {
+    const int buf = it & 1;
+    // tile boundary, reached by every wave on every path: this wave's share
+    // of tile `it` has landed; behind the barrier everyone's has, and tile
+    // it - 1 is consumed
+    pf_wait_loads();
+    __syncthreads();
+    if (kb + PF_KEY_TILE < r1) {
+      const int64_t off = src.off(kb + PF_KEY_TILE, false);
+      pf_stage<D, false>(src.Kb + off, row_stride, kb + PF_KEY_TILE, last,
+                         k_lds[buf ^ 1], tid);
+      pf_stage<D, true>(src.Vb + off, row_stride, kb + PF_KEY_TILE, last,
+                        v_lds[buf ^ 1], tid);
+    }
+    src.prefetch(kb + 2 * PF_KEY_TILE, r1);
+    if (kb >= kend_w) continue;  // past this wave's last live row
+
+    // ---- St = K . Q^T: two 32-key C tiles
+    f32x16 st[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[t][r] = 0.f;
+#pragma unroll
+      for (int ds = 0; ds < DSL; ++ds)
+        st[t] = pf_mfma(pf_kfrag<D>(k_lds[buf], t * 32 + lo, ds * 32 + hi * 16),
+                        qf[ds], st[t]);
+    }
+    // ---- online softmax, lane-local: st[t][r] is key kb + t*32 + (r&3) +
+    // 8*(r>>2) + 4*hi of query row lo
+    if (kb + PF_KEY_TILE > lim_min) {  // wave-uniform: a step the mask bites
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kg = kb + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          st[t][r] = kg < lim ? st[t][r] * scale : PF_NEG;
+        }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[t][r] *= scale;
+    }
+    float tmax = PF_NEG;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[t][r]);
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float mnew = fmaxf(m_run, tmax);
+    if (__ballot(mnew > m_run)) {  // some row of the wave grew
+      const float alpha = __expf(m_run - mnew);  // 1 for rows that did not
+      l_run *= alpha;
+#pragma unroll
+      for (int dt = 0; dt < DT32; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o_acc[dt][r] *= alpha;
+      m_run = mnew;
+    }
+    // a row with no visible key yet subtracts 0: exp(-1e30) = 0 exactly
+    const float msub = m_run == PF_NEG ? 0.f : m_run;
+    float psum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = __expf(st[t][r] - msub);
+        st[t][r] = p;
+        psum += p;
+      }
+    l_run += psum;  // this lane's half of the row; pair-reduced at the end
+
+    // ---- P^T fragments (pf_pfrag): 16 keys each, natural key order
+    short8 pa[4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int kst = 0; kst < 2; ++kst) {
+        const int g0 = 8 * kst, g1 = 8 * kst + 4;
+        pa[t * 2 + kst] = pf_pfrag(st[t][g0], st[t][g0 + 1], st[t][g0 + 2],
+                                   st[t][g0 + 3], st[t][g1], st[t][g1 + 1],
+                                   st[t][g1 + 2], st[t][g1 + 3]);
+      }
+    // ---- O^T += V^T . P^T
+#pragma unroll
+    for (int dt = 0; dt < DT32; ++dt)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        o_acc[dt] = pf_mfma(pf_vfrag<D>(v_lds[buf], ks, dt, lane), pa[ks],
+                            o_acc[dt]);
+  }
+
+  l_run += __shfl_xor(l_run, 32, 64);
+  if (myrow >= M) return;
+  pf_epilogue<D>(o_acc, m_run, l_run, live, O + qo_off, ws_o, ws_ml, myrow,
+                 nsplit, hi);
+}
+
 // grid B*T*H, D threads: splits combined in index order; dead queries
 // (t >= n, idle slots) are written as exact zeros.
 static __global__ void attn_prefill_merge_kernel(
@@ -236,4 +453,41 @@ static inline int pf_check_args(int64_t B, int64_t T, int64_t H, int64_t Hkv,
       Smax > 0x7fffffff - split_rows - PF_Q_ROWS || (nsplit > 1 && !ws))
     return hipErrorInvalidValue;
   return 0;
+}
+
+// Calls launch(D, GSH, grid) with the checked D in {64, 128} and GSH = log2 G
+// as integral constants; grid is (q-tiles, B*Hkv, nsplit). Callers must have
+// run pf_check_args: any other G lands on the G = 8 instantiation.
+template <class F>
+static void pf_dispatch(int64_t B, int64_t T, int64_t H, int64_t Hkv,
+                        int64_t D, int64_t nsplit, F launch) {
+  const int64_t G = H / Hkv;
+  const dim3 grid((unsigned)((T * G + PF_Q_ROWS - 1) / PF_Q_ROWS),
+                  (unsigned)(B * Hkv), (unsigned)nsplit);
+  auto with_d = [&](auto d) {
+    switch (G) {
+      case 1: launch(d, std::integral_constant<int, 0>{}, grid); break;
+      case 2: launch(d, std::integral_constant<int, 1>{}, grid); break;
+      case 4: launch(d, std::integral_constant<int, 2>{}, grid); break;
+      default: launch(d, std::integral_constant<int, 3>{}, grid); break;
+    }
+  };
+  if (D == 128)
+    with_d(std::integral_constant<int, 128>{});
+  else
+    with_d(std::integral_constant<int, 64>{});
+}
+
+// The merge launch (when there is something to merge) and the status of
+// every prefill entry point.
+static inline int pf_launch_merge(hipStream_t stream, const void* ws, void* O,
+                                  const void* lens, const void* n_new,
+                                  int64_t B, int64_t T, int64_t H, int64_t Hkv,
+                                  int64_t D, int64_t Smax, int64_t nsplit) {
+  if (nsplit > 1)
+    hipLaunchKernelGGL(attn_prefill_merge_kernel, dim3((unsigned)(B * T * H)),
+                       dim3((unsigned)D), 0, stream, (const float*)ws, (bf16*)O,
+                       (const int*)lens, (const int*)n_new, (int)B, (int)T,
+                       (int)H, (int)Hkv, (int)D, (int)Smax, (int)nsplit);
+  return (int)hipGetLastError();
 }

@@ -334,33 +334,6 @@ attn_prefill_ragged_fp8_kernel(
                  nsplit, hi);
 }
 
-template <int D, int GSH>
-static void pf8_launch(hipStream_t stream, dim3 grid, const void* Q,
-                       const void* K, const void* V, const void* Ks,
-                       const void* Vs, void* O, void* ws, const void* lens,
-                       const void* n_new, int T, int H, int Hkv, int Smax,
-                       int split_rows, float scale) {
-  hipLaunchKernelGGL((attn_prefill_ragged_fp8_kernel<D, GSH>), grid,
-                     dim3(PF_THREADS), 0, stream, (const bf16*)Q, (const u8*)K,
-                     (const u8*)V, (const float*)Ks, (const float*)Vs, (bf16*)O,
-                     (float*)ws, (const int*)lens, (const int*)n_new, T, H, Hkv,
-                     Smax, split_rows, scale);
-}
-
-template <int D>
-static void pf8_launch_g(int gsh, hipStream_t stream, dim3 grid, const void* Q,
-                         const void* K, const void* V, const void* Ks,
-                         const void* Vs, void* O, void* ws, const void* lens,
-                         const void* n_new, int T, int H, int Hkv, int Smax,
-                         int split_rows, float scale) {
-  switch (gsh) {
-    case 0: pf8_launch<D, 0>(stream, grid, Q, K, V, Ks, Vs, O, ws, lens, n_new, T, H, Hkv, Smax, split_rows, scale); break;
-    case 1: pf8_launch<D, 1>(stream, grid, Q, K, V, Ks, Vs, O, ws, lens, n_new, T, H, Hkv, Smax, split_rows, scale); break;
-    case 2: pf8_launch<D, 2>(stream, grid, Q, K, V, Ks, Vs, O, ws, lens, n_new, T, H, Hkv, Smax, split_rows, scale); break;
-    default: pf8_launch<D, 3>(stream, grid, Q, K, V, Ks, Vs, O, ws, lens, n_new, T, H, Hkv, Smax, split_rows, scale); break;
-  }
-}
-
 // The contract of prime_attn_prefill_ragged (split_rows, ws layout), with the
 // cache as e4m3 bytes K/V [B,Smax,Hkv,D] + fp32 k_scale/v_scale [B,Smax,Hkv].
 PRIME_API int prime_attn_prefill_ragged_fp8(
@@ -371,23 +344,15 @@ PRIME_API int prime_attn_prefill_ragged_fp8(
   if (pf_check_args(B, T, H, Hkv, Smax, D, split_rows, ws, lens, n_new) ||
       !k_scale || !v_scale)
     return hipErrorInvalidValue;
-  const int64_t G = H / Hkv;
   const int64_t nsplit = (Smax + split_rows - 1) / split_rows;
-  const int64_t nqt = (T * G + PF_Q_ROWS - 1) / PF_Q_ROWS;
-  const int gsh = G == 1 ? 0 : (G == 2 ? 1 : (G == 4 ? 2 : 3));
-  const dim3 grid((unsigned)nqt, (unsigned)(B * Hkv), (unsigned)nsplit);
-  if (D == 128)
-    pf8_launch_g<128>(gsh, stream, grid, Q, K, V, k_scale, v_scale, O, ws, lens,
-                      n_new, (int)T, (int)H, (int)Hkv, (int)Smax,
-                      (int)split_rows, (float)scale);
-  else
-    pf8_launch_g<64>(gsh, stream, grid, Q, K, V, k_scale, v_scale, O, ws, lens,
-                     n_new, (int)T, (int)H, (int)Hkv, (int)Smax,
-                     (int)split_rows, (float)scale);
-  if (nsplit > 1)
-    hipLaunchKernelGGL(attn_prefill_merge_kernel, dim3((unsigned)(B * T * H)),
-                       dim3((unsigned)D), 0, stream, (const float*)ws, (bf16*)O,
-                       (const int*)lens, (const int*)n_new, (int)B, (int)T,
-                       (int)H, (int)Hkv, (int)D, (int)Smax, (int)nsplit);
-  return (int)hipGetLastError();
+  pf_dispatch(B, T, H, Hkv, D, nsplit, [&](auto d, auto gsh, dim3 grid) {
+    hipLaunchKernelGGL((attn_prefill_ragged_fp8_kernel<d(), gsh()>), grid,
+                       dim3(PF_THREADS), 0, stream, (const bf16*)Q,
+                       (const u8*)K, (const u8*)V, (const float*)k_scale,
+                       (const float*)v_scale, (bf16*)O, (float*)ws,
+                       (const int*)lens, (const int*)n_new, (int)T, (int)H,
+                       (int)Hkv, (int)Smax, (int)split_rows, (float)scale);
+  });
+  return pf_launch_merge(stream, ws, O, lens, n_new, B, T, H, Hkv, D, Smax,
+                         nsplit);
 }

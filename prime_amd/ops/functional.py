@@ -1206,6 +1206,37 @@ def _check_ragged_shape(H: int, Hkv: int, D: int) -> None:
             f"kv_heads={Hkv})")
 
 
+def _check_len_vecs(q, **vecs) -> None:
+    """lens / n_new of an attention op over q [B, ...]."""
+    for name, v in vecs.items():
+        if v.dtype != torch.int32 or v.shape != q.shape[:1] or v.device != q.device:
+            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+
+
+def _split_rows(split_rows, unit: int, default) -> int:
+    """The caller's split_rows, or default() for None: a positive multiple of
+    the kernel's chunk / key tile."""
+    if split_rows is None:
+        split_rows = default()
+    if split_rows <= 0 or split_rows % unit != 0:
+        raise ValueError(f"split_rows must be a positive multiple of "
+                         f"{unit} (got {split_rows})")
+    return split_rows
+
+
+def _split_ws(cache: dict, q, B, Hkv, rows, D, nsplit):
+    """fp32 partials of a split kernel with `rows` query rows per kv head: one
+    workspace per shape, reused, so a captured graph sees stable pointers. The
+    bf16, fp8 and paged variants of an op share it (same key, and the ops run
+    in stream order)."""
+    key = (B, Hkv, rows, D, nsplit, q.device.index)
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = torch.empty(B * Hkv, nsplit, rows * (D + 2),
+                                      device=q.device, dtype=torch.float32)
+    return ws
+
+
 def attn_decode_ragged(q, k_cache, v_cache, lens, split_rows=None) -> torch.Tensor:
     """Single-token decode with per-sequence lengths: q [B,H,D] (or
     [B,1,H,D]); sequence b attends to rows [0, lens[b]) of its own caches
@@ -1217,8 +1248,7 @@ def attn_decode_ragged(q, k_cache, v_cache, lens, split_rows=None) -> torch.Tens
         q = q.squeeze(1)
     B, H, D = q.shape
     _, Smax, Hkv, _ = k_cache.shape
-    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != q.device:
-        raise ValueError("lens must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens)
     if not _is_hip(q):
         o = torch.zeros_like(q)
         for b, n in enumerate(lens.tolist()):
@@ -1230,19 +1260,12 @@ def attn_decode_ragged(q, k_cache, v_cache, lens, split_rows=None) -> torch.Tens
     _check_ragged_shape(H, Hkv, D)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("attn_decode_ragged needs contiguous KV caches")
-    if split_rows is None:
-        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % DECODE_RAGGED_CHUNK != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{DECODE_RAGGED_CHUNK} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, DECODE_RAGGED_CHUNK,
+        lambda: decode_ragged_split(B, Hkv, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
     G = H // Hkv
-    # one workspace per shape, reused: a captured graph sees stable pointers
-    key = (B, Hkv, G, D, nsplit, q.device.index)
-    ws = _RAGGED_WS.get(key)
-    if ws is None:
-        ws = _RAGGED_WS[key] = torch.empty(
-            B * Hkv, nsplit, G * (D + 2), device=q.device, dtype=torch.float32)
+    ws = _split_ws(_RAGGED_WS, q, B, Hkv, G, D, nsplit)
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -1341,9 +1364,7 @@ def attn_decode_ragged_multi(q, k_cache, v_cache, lens, n_new,
         raise ValueError("attn_decode_ragged_multi needs q [B,T,H,D]")
     B, T, H, D = q.shape
     _, Smax, Hkv, _ = k_cache.shape
-    for name, v in (("lens", lens), ("n_new", n_new)):
-        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
-            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens, n_new=n_new)
     if not _is_hip(q):
         o = torch.zeros_like(q)
         for b, (L, n) in enumerate(zip(lens.tolist(), n_new.tolist())):
@@ -1363,19 +1384,11 @@ def attn_decode_ragged_multi(q, k_cache, v_cache, lens, n_new,
             f"kv_heads={Hkv}, T={T})")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("attn_decode_ragged_multi needs contiguous KV caches")
-    if split_rows is None:
-        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % DECODE_MULTI_CHUNK != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{DECODE_MULTI_CHUNK} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, DECODE_MULTI_CHUNK,
+        lambda: decode_ragged_split(B, Hkv, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
-    # one workspace per shape, reused: a captured graph sees stable pointers
-    key = (B, Hkv, T * G, D, nsplit, q.device.index)
-    ws = _MULTI_WS.get(key)
-    if ws is None:
-        ws = _MULTI_WS[key] = torch.empty(
-            B * Hkv, nsplit, T * G * (D + 2), device=q.device,
-            dtype=torch.float32)
+    ws = _split_ws(_MULTI_WS, q, B, Hkv, T * G, D, nsplit)
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -1479,9 +1492,7 @@ def attn_prefill_ragged(q, k_cache, v_cache, lens, n_new,
         raise ValueError("attn_prefill_ragged needs q [B,T,H,D]")
     B, T, H, D = q.shape
     _, Smax, Hkv, _ = k_cache.shape
-    for name, v in (("lens", lens), ("n_new", n_new)):
-        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
-            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens, n_new=n_new)
     if not _is_hip(q):
         o = torch.zeros_like(q)
         for b, (L, n) in enumerate(zip(lens.tolist(), n_new.tolist())):
@@ -1499,21 +1510,12 @@ def attn_prefill_ragged(q, k_cache, v_cache, lens, n_new,
             f"heads={H}, kv_heads={Hkv}, T={T}, Smax={Smax})")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("attn_prefill_ragged needs contiguous KV caches")
-    if split_rows is None:
-        split_rows = prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % PREFILL_KEY_TILE != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{PREFILL_KEY_TILE} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, PREFILL_KEY_TILE,
+        lambda: prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
-    ws = None
-    if nsplit > 1:
-        # one workspace per shape, reused: a captured graph sees stable pointers
-        key = (B, Hkv, T * G, D, nsplit, q.device.index)
-        ws = _PREFILL_WS.get(key)
-        if ws is None:
-            ws = _PREFILL_WS[key] = torch.empty(
-                B * Hkv * nsplit * T * G * (D + 2), device=q.device,
-                dtype=torch.float32)
+    ws = _split_ws(_PREFILL_WS, q, B, Hkv, T * G, D, nsplit) \
+        if nsplit > 1 else None
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -1738,8 +1740,7 @@ def attn_decode_ragged_fp8(q, cache: KVCacheFp8, lens, split_rows=None) -> torch
         q = q.squeeze(1)
     B, H, D = q.shape
     _, Smax, Hkv, _ = cache.k.shape
-    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != q.device:
-        raise ValueError("lens must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens)
     if not _is_hip(q):
         o = torch.zeros_like(q)
         for b, n in enumerate(lens.tolist()):
@@ -1752,19 +1753,12 @@ def attn_decode_ragged_fp8(q, cache: KVCacheFp8, lens, split_rows=None) -> torch
         return o
     _check_ragged_shape(H, Hkv, D)
     _fp8_cache_contiguous(cache, "attn_decode_ragged_fp8")
-    if split_rows is None:
-        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % DECODE_RAGGED_CHUNK != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{DECODE_RAGGED_CHUNK} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, DECODE_RAGGED_CHUNK,
+        lambda: decode_ragged_split(B, Hkv, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
     G = H // Hkv
-    # the bf16 op's workspace: same shape key, and the ops run in stream order
-    key = (B, Hkv, G, D, nsplit, q.device.index)
-    ws = _RAGGED_WS.get(key)
-    if ws is None:
-        ws = _RAGGED_WS[key] = torch.empty(
-            B * Hkv, nsplit, G * (D + 2), device=q.device, dtype=torch.float32)
+    ws = _split_ws(_RAGGED_WS, q, B, Hkv, G, D, nsplit)
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -1789,9 +1783,7 @@ def attn_decode_ragged_multi_fp8(q, cache: KVCacheFp8, lens, n_new,
         raise ValueError("attn_decode_ragged_multi_fp8 needs q [B,T,H,D]")
     B, T, H, D = q.shape
     _, Smax, Hkv, _ = cache.k.shape
-    for name, v in (("lens", lens), ("n_new", n_new)):
-        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
-            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens, n_new=n_new)
     if not _is_hip(q):
         o = torch.zeros_like(q)
         for b, (L, n) in enumerate(zip(lens.tolist(), n_new.tolist())):
@@ -1813,19 +1805,11 @@ def attn_decode_ragged_multi_fp8(q, cache: KVCacheFp8, lens, n_new,
             f"T * group <= {_MULTI_MAX_ROWS} (got head_dim={D}, heads={H}, "
             f"kv_heads={Hkv}, T={T})")
     _fp8_cache_contiguous(cache, "attn_decode_ragged_multi_fp8")
-    if split_rows is None:
-        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % DECODE_MULTI_CHUNK != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{DECODE_MULTI_CHUNK} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, DECODE_MULTI_CHUNK,
+        lambda: decode_ragged_split(B, Hkv, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
-    # the bf16 op's workspace: same shape key, and the ops run in stream order
-    key = (B, Hkv, T * G, D, nsplit, q.device.index)
-    ws = _MULTI_WS.get(key)
-    if ws is None:
-        ws = _MULTI_WS[key] = torch.empty(
-            B * Hkv, nsplit, T * G * (D + 2), device=q.device,
-            dtype=torch.float32)
+    ws = _split_ws(_MULTI_WS, q, B, Hkv, T * G, D, nsplit)
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -1903,9 +1887,7 @@ def attn_prefill_ragged_fp8(q, cache: KVCacheFp8, lens, n_new,
         raise ValueError("attn_prefill_ragged_fp8 needs q [B,T,H,D]")
     B, T, H, D = q.shape
     _, Smax, Hkv, _ = cache.k.shape
-    for name, v in (("lens", lens), ("n_new", n_new)):
-        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
-            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens, n_new=n_new)
     if not _is_hip(q):
         # the multi-token op's host path has no T limit
         return attn_decode_ragged_multi_fp8(q, cache, lens, n_new)
@@ -1916,21 +1898,12 @@ def attn_prefill_ragged_fp8(q, cache: KVCacheFp8, lens, n_new,
             f"group size in {_RAGGED_GROUPS} and 1 <= T <= Smax (got "
             f"head_dim={D}, heads={H}, kv_heads={Hkv}, T={T}, Smax={Smax})")
     _fp8_cache_contiguous(cache, "attn_prefill_ragged_fp8")
-    if split_rows is None:
-        split_rows = prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % PREFILL_KEY_TILE != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{PREFILL_KEY_TILE} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, PREFILL_KEY_TILE,
+        lambda: prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
-    ws = None
-    if nsplit > 1:
-        # the bf16 op's workspace: same shape key, and the ops run in stream order
-        key = (B, Hkv, T * G, D, nsplit, q.device.index)
-        ws = _PREFILL_WS.get(key)
-        if ws is None:
-            ws = _PREFILL_WS[key] = torch.empty(
-                B * Hkv * nsplit * T * G * (D + 2), device=q.device,
-                dtype=torch.float32)
+    ws = _split_ws(_PREFILL_WS, q, B, Hkv, T * G, D, nsplit) \
+        if nsplit > 1 else None
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -2070,23 +2043,16 @@ def attn_decode_ragged_paged(q, cache: KVCachePaged, lens,
         raise ValueError(f"attn_decode_ragged_paged: q {tuple(q.shape)} does not "
                          f"match pools {tuple(cache.k.shape)} / table "
                          f"{tuple(cache.table.shape)}")
-    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != q.device:
-        raise ValueError("lens must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens)
     if not _is_hip(q):
         return attn_decode_ragged(q, *kv_paged_gather(cache), lens)
     _check_ragged_shape(H, Hkv, D)
-    if split_rows is None:
-        split_rows = decode_ragged_split(B, Hkv, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % DECODE_RAGGED_CHUNK != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{DECODE_RAGGED_CHUNK} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, DECODE_RAGGED_CHUNK,
+        lambda: decode_ragged_split(B, Hkv, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
     G = H // Hkv
-    key = (B, Hkv, G, D, nsplit, q.device.index)  # the sibling's workspace
-    ws = _RAGGED_WS.get(key)
-    if ws is None:
-        ws = _RAGGED_WS[key] = torch.empty(
-            B * Hkv, nsplit, G * (D + 2), device=q.device, dtype=torch.float32)
+    ws = _split_ws(_RAGGED_WS, q, B, Hkv, G, D, nsplit)
     q = q.contiguous()
     o = torch.empty_like(q)
     check(
@@ -2117,9 +2083,7 @@ def attn_prefill_ragged_paged(q, cache: KVCachePaged, lens, n_new,
         raise ValueError(f"attn_prefill_ragged_paged: q {tuple(q.shape)} does "
                          f"not match pools {tuple(cache.k.shape)} / table "
                          f"{tuple(cache.table.shape)}")
-    for name, v in (("lens", lens), ("n_new", n_new)):
-        if v.dtype != torch.int32 or v.shape != (B,) or v.device != q.device:
-            raise ValueError(f"{name} must be an int32 [B] tensor on q's device")
+    _check_len_vecs(q, lens=lens, n_new=n_new)
     if not _is_hip(q):
         return attn_prefill_ragged(q, *kv_paged_gather(cache), lens, n_new)
     G = H // Hkv if H % Hkv == 0 else 0
@@ -2128,20 +2092,12 @@ def attn_prefill_ragged_paged(q, cache: KVCachePaged, lens, n_new,
             f"attn_prefill_ragged_paged needs head_dim in {{64, 128}}, a GQA "
             f"group size in {_RAGGED_GROUPS} and 1 <= T <= Smax (got "
             f"head_dim={D}, heads={H}, kv_heads={Hkv}, T={T}, Smax={Smax})")
-    if split_rows is None:
-        split_rows = prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device))
-    if split_rows <= 0 or split_rows % PREFILL_KEY_TILE != 0:
-        raise ValueError(f"split_rows must be a positive multiple of "
-                         f"{PREFILL_KEY_TILE} (got {split_rows})")
+    split_rows = _split_rows(
+        split_rows, PREFILL_KEY_TILE,
+        lambda: prefill_ragged_split(B, Hkv, T, G, Smax, _n_cu(q.device)))
     nsplit = -(-Smax // split_rows)
-    ws = None
-    if nsplit > 1:
-        key = (B, Hkv, T * G, D, nsplit, q.device.index)  # the sibling's
-        ws = _PREFILL_WS.get(key)
-        if ws is None:
-            ws = _PREFILL_WS[key] = torch.empty(
-                B * Hkv * nsplit * T * G * (D + 2), device=q.device,
-                dtype=torch.float32)
+    ws = _split_ws(_PREFILL_WS, q, B, Hkv, T * G, D, nsplit) \
+        if nsplit > 1 else None
     q = q.contiguous()
     o = torch.empty_like(q)
     check(

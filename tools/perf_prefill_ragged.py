@@ -14,7 +14,8 @@ process under its own time limit, and the first child that fails, faults or
 runs out of time ends the run. Inside a child both paths are warmed, then
 alternated `--repeats` times, event-timed. The calls rotate over enough
 separate KV caches (>= 1 GiB in total) that a timing is not served from the
-256 MiB Infinity Cache. H=32, Hkv=8 (G=4), D=128, bf16. TF/s is the
+256 MiB Infinity Cache. H=32, Hkv=8 (G=4), D=128 (--head-dim 64 for the
+D=64 kernels), bf16. TF/s is the
 shape-derived count 4*B*H*D*sum_t(keys of token t) over the median time.
 
 --fp8: attn_prefill_ragged_fp8 over KVCacheFp8 caches (kv_store_fp8 of the
@@ -115,7 +116,8 @@ def us(xs):
 
 def run_case(args, B, P, T, fp8):
     """One case in a fresh child process; its JSON result."""
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--step",
+    cmd = [sys.executable, str(Path(__file__).resolve()), "--head-dim", str(D),
+           "--step",
            json.dumps({"B": B, "P": P, "T": T, "iters": args.iters,
                        "repeats": args.repeats, "fp8": fp8})]
     r = subprocess.run(cmd, capture_output=True, text=True,
@@ -149,6 +151,7 @@ def main_fp8(args):
 
 
 def main():
+    global D
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
@@ -156,8 +159,10 @@ def main():
                     help="time limit of each child process in seconds")
     ap.add_argument("--fp8", action="store_true",
                     help="the fp8-cache kernel (see the module docstring)")
+    ap.add_argument("--head-dim", type=int, default=D, choices=(64, 128))
     ap.add_argument("--step", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    D = args.head_dim
     if args.step:  # child: one case, one JSON line
         import torch
 
